@@ -13,6 +13,8 @@ bucketed RCCL gradient reduction -> optimizer step. Weak scaling: per-GPU work i
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
   python bench.py --impl torch                      # stock torch DDP + torch.optim (comparison)
   python bench.py --api accelerate                  # the same step through Accelerator.prepare()
+  python bench.py --full                            # plus the post-measurement diagnostics
+  python bench.py --dump-outputs DIR                # plus the last step's outputs as DIR/*.npy
 
 Execution: at world size > 1 the whole step is captured into a hipGraph and replayed, so the
 bucket collectives run on the communicator's side stream and overlap backward (inside a graph the
@@ -25,12 +27,17 @@ mode. A captured toy-MLP replay runs FOUR training steps (``--graph-steps 4``, e
 batch gather and update; an epoch boundary always falls between replays), which pays the
 graph-launch gap once per four steps; the trajectory is bit-identical to one step per replay.
 
-Diagnostics (after the timed region, in the JSON line's "diagnostics"): at world size > 1 the
-collectives of one step alone (``comm_ms``), the same captured step with its collectives turned
-into no-ops (``compute_ms``), the share of the collective time hidden behind compute
-(``overlap_pct``) and a short RCCL bus-bandwidth sweep; at world size 1 the single-GPU rehearsal
-of the multi-GPU schedule (``rehearsal_ms``: RCCL collectives kept, per-bucket fused update,
-captured step).
+A plain run sets up, warms up, times the K steps, writes its outputs when ``--dump-outputs DIR``
+is given (the last timed step's loss and the parameters it left, as ``DIR/<name>.npy``; the same
+arguments give the same inputs in every run, so two builds compare output for output) and prints
+the record. Everything measured beyond the headline figure runs only with ``--full``.
+
+Diagnostics (``--full``; after the timed region, in the JSON line's "diagnostics"): at world
+size > 1 the collectives of one step alone (``comm_ms``), the same captured step with its
+collectives turned into no-ops (``compute_ms``), the share of the collective time hidden behind
+compute (``overlap_pct``) and a short RCCL bus-bandwidth sweep; at world size 1 the single-GPU
+rehearsal of the multi-GPU schedule (``rehearsal_ms``: RCCL collectives kept, per-bucket fused
+update, captured step).
 
 Timing: a device warm-up (``--device-warmup-ms`` of training steps on a scratch replica of the
 model for the toy MLP, dummy GEMMs for the CNNs; ``--warmup-mode``) that touches no state of the
@@ -92,8 +99,15 @@ def parse():
                     help="device warm-up before the W warm-up steps: training steps of a scratch "
                          "replica of the model (tdp) or dummy GEMMs; auto = scratch for the toy "
                          "MLP, GEMMs for the CNNs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the post-measurement diagnostics (comm / "
+                         "compute / rehearsal, runs of their own); a plain run only sets up, warms "
+                         "up, times the steps and prints the record")
     ap.add_argument("--no-diag", action="store_true",
-                    help="skip the post-measurement diagnostics (comm / compute / rehearsal)")
+                    help="skip the post-measurement diagnostics even with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (its "
+                         "loss and the parameters it left, see dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--syncbn", action="store_true", help="toy MLP + SyncBatchNorm config")
     ap.add_argument("--model", choices=["toy_mlp", "alexnet", "resnet50"], default="toy_mlp",
                     help="toy_mlp = the headline config; alexnet / resnet50 = the CNN configs")
@@ -269,6 +283,47 @@ def _time_steps(step, n):
         step()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1000.0 / n
+
+
+DUMP_BUDGET = 12 * 2 ** 20  # elements over all dumped arrays (48 MiB of float32)
+
+
+def _sample_cap(sizes, budget: int) -> int:
+    """Largest per-array element count c with sum(min(size, c)) <= budget."""
+    left = budget
+    sizes = sorted(sizes)
+    for i, s in enumerate(sizes):
+        share = left // (len(sizes) - i)
+        if s > share:
+            return share
+        left -= s
+    return sizes[-1] if sizes else 0
+
+
+def dump_outputs(path, loss, module) -> None:
+    """``--dump-outputs DIR``: what the last timed step handed its caller -- its loss
+    (``loss.npy``) and the parameters it left behind (``<parameter name>.npy``, this rank's
+    replica or shard) -- as float32. Arrays are written whole while they fit DUMP_BUDGET elements
+    together; otherwise the larger ones are a fixed sample of their flattened elements (indices
+    drawn with replacement from a generator seeded by the parameter's position, the same from
+    run to run and from build to build)."""
+    import numpy as np
+
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    named = [(n, p.detach()) for n, p in module.named_parameters()]
+    cap = _sample_cap([t.numel() for _, t in named], DUMP_BUDGET - 1)
+    np.save(d / "loss.npy", loss.detach().float().cpu().numpy())
+    for i, (n, t) in enumerate(named):
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator().manual_seed(1000 + i)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g)
+            flat = flat.index_select(0, idx.to(flat.device))
+            arr = flat.float().cpu().numpy()
+        else:
+            arr = t.float().cpu().numpy()
+        np.save(d / f"{n}.npy", arr)
 
 
 def predicted_comm(a, ddp, world, sweep) -> dict:
@@ -859,6 +914,8 @@ def build_tdp(a, ctx, cfg, attempt, fallbacks, fault):
     step.graph_steps = a.graph_steps if run_pair[0] is not None else (1 if graph else 0)
     return types.SimpleNamespace(ddp=ddp, tp=tp, opt=opt, fused=fused, step=step, run=run,
                                  graph=graph, rung=cfg["name"],
+                                 module=tp if tp is not None else
+                                 (model if a.api == "accelerate" else ddp),
                                  build_rehearsal=None if (a.api == "accelerate" or tp is not None)
                                  else build_rehearsal)
 
@@ -1130,6 +1187,9 @@ def main():
     value = a.batch * world * a.steps / dt
     base, base_src = baseline_for(world, a.impl, a.syncbn, a.model)
     final_loss = round(float(loss.item()), 5)
+    if a.dump_outputs and rank == 0:
+        # before any diagnostics: they run further steps on the measured model
+        dump_outputs(a.dump_outputs, loss, job.module if a.impl == "tdp" else ddp)
     sync = None
     if a.impl == "tdp" and ddp is not None:
         # self-report for the multi-GPU record: did every rank end with bit-identical
@@ -1246,7 +1306,7 @@ def main():
 
     diag = None
     tp_job = job if (a.impl == "tdp" and getattr(job, "tp", None) is not None) else None
-    if tp_job is not None and use_gpu and not a.no_diag:
+    if tp_job is not None and use_gpu and a.full and not a.no_diag:
         limit = float(os.environ.get("TDP_DIAG_TIMEOUT_S", "120"))
 
         def expire_tp():
@@ -1262,7 +1322,7 @@ def main():
         except Exception as e:  # diagnostics never cost the measurement
             diag = {"error": repr(e)[:300]}
         timer.cancel()
-    if a.impl == "tdp" and ddp is not None and use_gpu and not a.no_diag:
+    if a.impl == "tdp" and ddp is not None and use_gpu and a.full and not a.no_diag:
         # The measurement is final here. Diagnostics run more collectives, and a peer that
         # stalls in them must not cost the result: past the deadline every rank exits 0, and
         # rank 0 first prints the record without them.

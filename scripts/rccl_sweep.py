@@ -7,7 +7,7 @@
 One JSON line per (collective, size) on rank 0: all-reduce / reduce-scatter / all-gather bus
 bandwidth (nccl-tests convention) from 1 KiB to 256 MiB in powers of 4, plus the bucket-plan
 consequence for the toy MLP's two buckets (64.2 / 144 MiB). The same measurement runs in small
-form inside bench.py at world size > 1 (diagnostics.busbw_GBps).
+form inside ``bench.py --full`` at world size > 1 (diagnostics.busbw_GBps).
 """
 from __future__ import annotations
 

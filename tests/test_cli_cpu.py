@@ -229,3 +229,53 @@ def test_bench_parallel_auto_needs_a_ddp_rung():
     r = _bench_cpu2({"TDP_BENCH_FAULT": "warmup@*"}, "--parallel", "auto", "--select-steps", "1")
     assert r.returncode != 0 and r.stdout.strip() == ""
     assert "every rung of the fallback ladder failed" in r.stderr
+
+
+def test_bench_dump_outputs_is_repeatable(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss and parameters as float32 .npy files; the
+    same arguments give the same inputs, so two runs agree bit for bit. A plain run carries no
+    diagnostics."""
+    import numpy as np
+
+    env = {k: None for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"d{i}"
+        r = _run(["bench.py", "--cpu", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                  "--dataset", "128", "--batch", "16", "--mlp-dims", "64,32,32",
+                  "--dump-outputs", str(d)], env_extra=env)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and "diagnostics" not in rec
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+        assert float(dumps[-1]["loss.npy"]) == pytest.approx(rec["config"]["final_loss"], abs=1e-5)
+    assert set(dumps[0]) == {"loss.npy"} | {f"module.fc{k}.{w}.npy" for k in (1, 2, 3)
+                                            for w in ("weight", "bias")}
+    assert dumps[0]["module.fc1.weight.npy"].shape == (32, 64)
+    for name, arr in dumps[0].items():
+        assert arr.dtype == np.float32, name
+        assert np.array_equal(arr, dumps[1][name]), name
+
+
+def test_bench_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """Arrays that do not fit the budget together are dumped as a fixed sample: small ones whole,
+    the total within the budget, the same elements on every call."""
+    import numpy as np
+
+    import bench
+
+    assert bench._sample_cap([10, 100, 1000], 2000) == 1000
+    assert bench._sample_cap([10, 100, 1000], 510) == 400
+    assert bench._sample_cap([10, 100, 1000], 30) == 10
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 501)
+    torch.manual_seed(3)
+    m = torch.nn.Sequential(torch.nn.Linear(40, 50), torch.nn.Linear(50, 2))
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, torch.tensor(1.5), m)
+    a = {f.name: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    # 500 elements for the parameters: 2 + 50 + 100 whole, 348 left for the 2000 of 0.weight
+    assert a["0.weight.npy"].shape == (348,) and a["1.weight.npy"].shape == (2, 50)
+    assert sum(v.size for v in a.values()) <= 501
+    assert np.isin(a["0.weight.npy"], m[0].weight.detach().numpy()).all()
+    for name, arr in a.items():
+        assert np.array_equal(arr, np.load(tmp_path / "b" / name)), name

@@ -390,7 +390,8 @@ def test_bench_diagnostics_deadline():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, TDP_DIAG_MULTI="1", TDP_DIAG_TIMEOUT_S="0.001")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mlp-dims",
-                        "256,128,128", "--steps", "3", "--warmup", "1", "--dataset", "512"],
+                        "256,128,128", "--steps", "3", "--warmup", "1", "--dataset", "512",
+                        "--full"],
                        env=env, capture_output=True, text=True, timeout=110, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

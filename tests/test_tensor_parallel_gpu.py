@@ -63,7 +63,7 @@ def _peer_bench(*args, diag=False):
     env.update(TDP_GPU_PEER="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
            "--warmup", "2", "--mlp-dims", "1024,512,512", "--dataset", "1024", "--batch", "32",
-           "--device-warmup-ms", "0", *([] if diag else ["--no-diag"]), *args]
+           "--device-warmup-ms", "0", "--full" if diag else "--no-diag", *args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
