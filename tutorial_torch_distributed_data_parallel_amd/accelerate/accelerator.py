@@ -23,6 +23,7 @@ import os
 import torch
 
 from ..data.sampler import BatchShardSampler
+from ..ops.precision import autocast as _autocast
 from ..data.synthetic import DeviceLoader
 from ..parallel import runtime as rt
 from ..parallel.arena import flatten_module
@@ -144,9 +145,22 @@ def _to_device(batch, dev):
     return batch
 
 
+MIXED_PRECISION_MODES = ("no", "bf16")
+
+
 class Accelerator:
     def __init__(self, cpu: bool = False, gradient_accumulation_steps: int = 1,
-                 even_batches: bool = True, ddp_kwargs: dict | None = None):
+                 even_batches: bool = True, ddp_kwargs: dict | None = None,
+                 mixed_precision: str | None = None):
+        # None reads ACCELERATE_MIXED_PRECISION, as Accelerate's state does; else "no"
+        if mixed_precision is None:
+            mixed_precision = os.environ.get("ACCELERATE_MIXED_PRECISION", "no") or "no"
+        mixed_precision = str(mixed_precision).lower()
+        if mixed_precision not in MIXED_PRECISION_MODES:
+            raise ValueError(f"mixed_precision={mixed_precision!r} is not supported: choose one "
+                             f"of {list(MIXED_PRECISION_MODES)} (fp16 and fp8 are not "
+                             "implemented)")
+        self._mixed_precision = mixed_precision
         if not rt.is_initialized():
             multi = int(os.environ.get("WORLD_SIZE", "1")) > 1 or "LOCAL_RANK" in os.environ
             backend = "gloo" if (cpu or not torch.cuda.is_available()) else "nccl"
@@ -157,7 +171,10 @@ class Accelerator:
         self.device = rt.device()
         self.gradient_accumulation_steps = max(1, int(gradient_accumulation_steps))
         self.even_batches = even_batches
-        self.ddp_kwargs = ddp_kwargs or {}
+        self.ddp_kwargs = dict(ddp_kwargs or {})
+        if mixed_precision == "bf16":
+            # the bf16 Linear computes its own weight gradient: no factored synchronisation
+            self.ddp_kwargs.setdefault("factor_sync", False)
         self._step = 0
         self.sync_gradients = True
         self.end_of_dataloader = False
@@ -190,6 +207,17 @@ class Accelerator:
         return "MULTI_GPU" if (self.num_processes > 1 and self.device.type == "cuda") else (
             "MULTI_CPU" if self.num_processes > 1 else "NO")
 
+    @property
+    def mixed_precision(self) -> str:
+        return self._mixed_precision
+
+    def autocast(self):
+        """Context manager: ``tdp.autocast`` under ``mixed_precision="bf16"``, a no-op under
+        ``"no"``."""
+        if self._mixed_precision == "bf16":
+            return _autocast()
+        return contextlib.nullcontext()
+
     def print(self, *a, **k):
         if self.is_local_main_process:
             print(*a, **k)
@@ -221,6 +249,10 @@ class Accelerator:
             self._hidden[id(model)] = d
         else:
             flatten_module(model)  # single CPU process: still one flat arena for the flat step
+        if self._mixed_precision == "bf16" and not getattr(model, "_tdp_autocast_fwd", False):
+            # as Accelerate does: the prepared model's forward runs under autocast
+            model.forward = _autocast()(model.forward)
+            model._tdp_autocast_fwd = True
         self._models.append(model)
         return model
 

@@ -97,7 +97,8 @@ def basic_ddp_training_loop(rank: int, world_size: int, save_dir: str, optional_
     from .parallel import DDP, destroy_process_group, init_process_group
     from .parallel import runtime as rt
     from .train import run_training_loop
-    from .utils.config import tristate
+    from .ops.precision import autocast
+    from .utils.config import mixed_precision_of, tristate
     from .utils.seed import set_seed_based_on_rank
 
     print(f"Running DDP checkpoint example on rank {rank}.")
@@ -114,22 +115,26 @@ def basic_ddp_training_loop(rank: int, world_size: int, save_dir: str, optional_
     test_loader = _loader(train_cfg, test_ds, train_cfg["test_batch_size"], test_sampler, device,
                           train=False)
     model = build_model(train_cfg["model"], device=device)
+    bf16 = mixed_precision_of(train_cfg.get("mixed_precision")) == "bf16"
+    # the bf16 Linear computes its own weight gradient: no factored synchronisation
     ddp_model = DDP(model, device_ids=[device.index] if device.type == "cuda" else None,
-                    bucket_cap_mb=train_cfg.get("bucket_cap_mb"))
+                    bucket_cap_mb=train_cfg.get("bucket_cap_mb"),
+                    **({"factor_sync": False} if bf16 else {}))
     criterion = tnn.CrossEntropyLoss()
     optimizer = _optimizer(train_cfg, ddp_model.parameters())
     if _want_fused(train_cfg, device):
         # the update runs inside the gradient reduction (per bucket, sharded over ranks; in the
         # weight-gradient GEMM epilogues at world size 1); optimizer.step() becomes a no-op
         ddp_model.register_fused_optimizer(optimizer)
-    run_training_loop(ddp_model, train_loader, train_sampler, test_loader, criterion, optimizer,
-                      device, rank, save_dir, num_epochs=train_cfg["num_epochs"],
-                      capture=tristate(train_cfg.get("capture")),
-                      checkpoint_epoch=train_cfg["checkpoint_epoch"],
-                      set_epoch=optional_args.get("set_epoch", True),
-                      print_rand=optional_args.get("print_rand", False),
-                      max_steps_per_epoch=train_cfg.get("max_steps_per_epoch"),
-                      json_log=os.path.join(save_dir, "metrics.jsonl") if rank == 0 else None)
+    with autocast(enabled=bf16):  # train and eval steps alike
+        run_training_loop(ddp_model, train_loader, train_sampler, test_loader, criterion,
+                          optimizer, device, rank, save_dir, num_epochs=train_cfg["num_epochs"],
+                          capture=tristate(train_cfg.get("capture")),
+                          checkpoint_epoch=train_cfg["checkpoint_epoch"],
+                          set_epoch=optional_args.get("set_epoch", True),
+                          print_rand=optional_args.get("print_rand", False),
+                          max_steps_per_epoch=train_cfg.get("max_steps_per_epoch"),
+                          json_log=os.path.join(save_dir, "metrics.jsonl") if rank == 0 else None)
     destroy_process_group()
 
 
@@ -171,7 +176,9 @@ def train_accelerate(argv=None):
 
     _, s = _settings(argv, "Run script based on local_settings.yaml file.")
     t = s["train"]
-    accelerator = Accelerator()
+    # ("no" leaves the choice to ACCELERATE_MIXED_PRECISION, as Accelerate's launcher does)
+    accelerator = Accelerator(
+        mixed_precision=t["mixed_precision"] if t["mixed_precision"] != "no" else None)
     device = accelerator.device
     train_ds, test_ds = _datasets(t, device)
     # no sampler, no shuffle (R11)

@@ -100,6 +100,69 @@ void gemm_f32_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, bo
   if (gate_after) gate_inplace(a.C, a.ldc, g, gate->stride(0), M, N, cur_stream());
 }
 
+// Mixed-precision GEMM (gemm_bf16.hip): fp32 tensors, operands rounded once to bf16, fp32
+// accumulation. Layouts as gemm_f32_op.
+GemmBf16Args gemm_bf16_args(const Tensor& A, const Tensor& B, const Tensor& C, bool a_kcontig,
+                            bool b_kcontig) {
+  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C);
+  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C);
+  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_ROWMAJOR(C);
+  const int M = (int)C.size(0), N = (int)C.size(1);
+  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1, "gemm_bf16: empty operand");
+  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
+  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
+  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
+  GemmBf16Args a;
+  a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
+  a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = C.stride(0);
+  a.M = M; a.N = N; a.K = K;
+  a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
+  a.num_cus = num_cus(C.get_device());
+  return a;
+}
+
+void gemm_bf16_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, bool b_kcontig,
+                  const c10::optional<Tensor>& bias, bool relu, const c10::optional<Tensor>& gate,
+                  const c10::optional<Tensor>& rowsum, double beta) {
+  GemmBf16Args a = gemm_bf16_args(A, B, C, a_kcontig, b_kcontig);
+  TORCH_CHECK(beta == 0.0 || beta == 1.0, "gemm_bf16: beta must be 0 or 1");
+  if (bias.has_value() && bias->defined()) {
+    CHECK_GPU(*bias); CHECK_F32(*bias); CHECK_CONTIG(*bias);
+    TORCH_CHECK(bias->numel() == a.N, "gemm: bias must have N elements");
+    a.bias = bias->data_ptr<float>();
+  }
+  if (rowsum.has_value() && rowsum->defined()) {
+    CHECK_GPU(*rowsum); CHECK_F32(*rowsum); CHECK_CONTIG(*rowsum);
+    TORCH_CHECK(rowsum->numel() == a.M, "gemm: rowsum must have M elements");
+    a.rowsum = rowsum->data_ptr<float>();
+  }
+  if (gate.has_value() && gate->defined()) {
+    CHECK_GPU(*gate); CHECK_F32(*gate); CHECK_ROWMAJOR(*gate);
+    TORCH_CHECK(gate->size(0) == a.M && gate->size(1) == a.N, "gemm: gate must have C's shape");
+    a.gate = gate->data_ptr<float>();
+    a.ldgate = gate->stride(0);
+  }
+  a.beta = (float)beta;
+  a.relu = relu;
+  const GemmBf16Plan plan = gemm_bf16_plan(a, a.num_cus);
+  Tensor ws;
+  if (plan.ws_floats > 0) {
+    ws = at::empty({plan.ws_floats}, C.options());
+    a.ws = ws.data_ptr<float>();
+    a.ws_floats = plan.ws_floats;
+  }
+  gemm_bf16(a, cur_stream());
+}
+
+// {splits, k_per_split, guarded} gemm_bf16 would use for these operands
+std::vector<int64_t> gemm_bf16_plan_op(const Tensor& A, const Tensor& B, const Tensor& C,
+                                       bool a_kcontig, bool b_kcontig) {
+  const GemmBf16Args a = gemm_bf16_args(A, B, C, a_kcontig, b_kcontig);
+  const GemmBf16Plan plan = gemm_bf16_plan(a, a.num_cus);
+  return {plan.splits, plan.k_per_split, plan.guarded ? 1 : 0};
+}
+
 // Returns whether the epilogue ran. Weight-gradient GEMM whose epilogue applies the DDP's fused optimizer to arena elements
 // [offset, offset + M*N) instead of storing the gradient into C (world size 1, see
 // RcclBackend::epilogue_opt). C must be that contiguous arena slice (its contents are left as
@@ -1773,6 +1836,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("a_kcontig"), py::arg("b_kcontig"), py::arg("mask") = py::none(),
         py::arg("bias") = py::none(), py::arg("rowsum") = py::none(), py::arg("beta") = 0.0,
         py::arg("rowsum_beta") = 0.0, py::arg("relu") = false, py::arg("gate") = py::none());
+  m.def("gemm_bf16", &gemm_bf16_op, py::arg("A"), py::arg("B"), py::arg("C"),
+        py::arg("a_kcontig"), py::arg("b_kcontig"), py::arg("bias") = py::none(),
+        py::arg("relu") = false, py::arg("gate") = py::none(), py::arg("rowsum") = py::none(),
+        py::arg("beta") = 0.0);
+  m.def("gemm_bf16_plan", &gemm_bf16_plan_op, py::arg("A"), py::arg("B"), py::arg("C"),
+        py::arg("a_kcontig"), py::arg("b_kcontig"));
   m.def("gemm_f32_opt", &gemm_f32_opt_op, py::arg("A"), py::arg("B"), py::arg("C"),
         py::arg("a_kcontig"), py::arg("b_kcontig"), py::arg("backend"), py::arg("offset"),
         py::arg("rowsum") = py::none(), py::arg("rowsum_beta") = 0.0,

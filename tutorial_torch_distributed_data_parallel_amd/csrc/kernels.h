@@ -167,23 +167,35 @@ void gemm_f32_set_bm(int bm);
 // negative = keep. Returns the active {sgd, adam, persist, wgs}.
 std::vector<int> gemm_f32_set_opt_variant(int sgd, int adam, int persist, int wgs);
 
-// bf16-operand GEMM (AMP path): same contract, A/B bf16 (uint16 storage), C fp32 or bf16.
-struct GemmBF16Args {
-  const uint16_t* A = nullptr;
-  const uint16_t* B = nullptr;
-  void* C = nullptr;
-  bool c_bf16 = false;
-  const uint16_t* mask = nullptr;
+// Mixed-precision GEMM (gemm_bf16.hip, the autocast path): fp32 tensors in memory, every operand
+// element rounded once to bf16 (RNE), one v_mfma_f32_32x32x16_bf16 per K16 step, fp32
+// accumulation and output.  C = bf16(A) . op(bf16(B)) (+ bias[N]) (+ beta*C, beta in {0, 1})
+// (ReLU) (* (gate > 0)), layouts as GemmF32Args. rowsum (optional, [M]) = sum_k of the UNROUNDED
+// fp32 A[m,k], in a fixed order (the bias gradient).
+struct GemmBf16Args {
+  const float* A = nullptr;
+  const float* B = nullptr;
+  float* C = nullptr;
   const float* bias = nullptr;
+  const float* gate = nullptr;
   float* rowsum = nullptr;
-  long lda = 0, ldb = 0, ldc = 0, ldmask = 0;
+  long lda = 0, ldb = 0, ldc = 0, ldgate = 0;
   int M = 0, N = 0, K = 0;
   bool a_kcontig = true, b_kcontig = true;
-  float beta = 0.f, rowsum_beta = 0.f;
+  float beta = 0.f;
   bool relu = false;
+  int num_cus = 256;    // CUs the plan fills
+  float* ws = nullptr;  // split-K workspace of ws_floats floats (gemm_bf16_plan says how many)
+  long ws_floats = 0;
 };
-GemmPlan gemm_bf16_plan(const GemmBF16Args& a, int num_cus);
-void gemm_bf16_run(const GemmBF16Args& a, const GemmPlan& plan, float* ws, hipStream_t s);
+struct GemmBf16Plan {
+  int splits = 1;
+  int k_per_split = 0;
+  long ws_floats = 0;    // split-K workspace needed (0 when splits == 1)
+  bool guarded = false;  // bounds-checked scalar loads (unaligned rows, K tail)
+};
+GemmBf16Plan gemm_bf16_plan(const GemmBf16Args& a, int num_cus);
+void gemm_bf16(const GemmBf16Args& a, hipStream_t s);
 
 // split-K combine + epilogue: C = epi(sum_z ws[z]) ; C fp32 or bf16
 void splitk_reduce(const float* ws, int splits, int M, int N, void* C, bool c_bf16, long ldc,

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from .._native import native
 from ._grad import (bias_epilogue, epilogue_target, factor_target, grad_dest, hand_off, needs,
                     note_use)
+from .precision import is_autocast_enabled
 
 # Skinny GEMMs (batch rows against thousands of features) read their activation operand from
 # its exact bf16 split planes (csrc/gemm_planes.hip): split once by the producer instead of once
@@ -334,6 +335,103 @@ class _LinearCpuFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+class _LinearBf16Fn(torch.autograd.Function):
+    """Linear under ``tdp.autocast`` (ops/precision.py): every GEMM operand element is rounded
+    once to bf16 and the products run as single bf16 MFMAs with fp32 accumulation
+    (csrc/gemm_bf16.hip); tensors, master weights and gradients stay float32, and the bias
+    gradient is summed from the unrounded output gradient. Chosen in forward, so backward follows
+    it whether or not the flag is still on. It consults neither the optimizer epilogue nor the
+    factored synchronisation: the update runs in the reducer's bucket pass or in ``opt.step()``.
+    The ``_tdp_relu_out`` / gated-dx conventions are _LinearFn's, so fp32 and bf16 layers mix in
+    one model; no planes are attached."""
+
+    @staticmethod
+    def forward(ctx, x2, weight, bias, relu: bool, gate_in: bool):
+        y = torch.empty((x2.shape[0], weight.shape[0]), device=x2.device, dtype=torch.float32)
+        native().gemm_bf16(x2, weight, y, True, True, bias=bias, relu=relu)
+        ctx.relu = relu
+        ctx.gate_in = gate_in
+        ctx.params = (weight, bias)
+        ctx.save_for_backward(x2, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = native()
+        x2, weight, y = ctx.saved_tensors
+        w_param, b_param = ctx.params
+        if dy.dim() != 2 or dy.stride(1) != 1:
+            dy = dy.contiguous()
+        dx = dw = None
+        want_db = b_param is not None and needs(ctx, 2)
+        db = grad_dest(b_param) if want_db else None
+        g = C.relu_bias_bwd(dy, y) if ctx.relu and not _pregated(dy, y) else dy
+        if needs(ctx, 0):
+            # dx[B, in] = g . W, with the producer's ReLU mask (x > 0) in the epilogue
+            dx = torch.empty_like(x2)
+            gate = x2 if ctx.gate_in else None
+            C.gemm_bf16(g, weight, dx, True, False, gate=gate)
+            if gate is not None:
+                _mark_gated(dx, x2)
+        if needs(ctx, 1):
+            # dW[out, in] = g^T . x, and db = the batch sum of the unrounded g
+            dw = grad_dest(w_param)
+            C.gemm_bf16(g, x2, dw, False, False, rowsum=db)
+        elif want_db:
+            C.relu_bias_bwd(g, None, db)
+        return dx, dw, db, None, None
+
+
+def _bf16r(t: torch.Tensor) -> torch.Tensor:
+    """``t`` with every element rounded to bf16 (round-to-nearest-even), as float32."""
+    return t.bfloat16().float()
+
+
+class _LinearBf16CpuFn(torch.autograd.Function):
+    """The CPU twin of _LinearBf16Fn in torch math: operands rounded to bf16, fp32 matmuls, the
+    bias gradient from the unrounded g, _LinearCpuFn's gradient routing."""
+
+    @staticmethod
+    def forward(ctx, x2, weight, bias, relu: bool, gate_in: bool):
+        y = F.linear(_bf16r(x2), _bf16r(weight), bias)
+        if relu:
+            y = F.relu(y)
+        ctx.relu = relu
+        ctx.gate_in = gate_in
+        ctx.params = (weight, bias)
+        ctx.save_for_backward(x2, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, weight, y = ctx.saved_tensors
+        w_param, b_param = ctx.params
+        g = dy * (y > 0) if ctx.relu and not _pregated(dy, y) else dy
+        dx = dw = None
+        want_db = b_param is not None and needs(ctx, 2)
+        db = grad_dest(b_param) if want_db else None
+        gr = _bf16r(g)
+        if needs(ctx, 0):
+            dx = gr @ _bf16r(weight)
+            if ctx.gate_in:
+                dx = dx * (x2 > 0)
+                _mark_gated(dx, x2)
+        if needs(ctx, 1):
+            dw = grad_dest(w_param)
+            dw.copy_(gr.t() @ _bf16r(x2))
+        if db is not None:
+            db.copy_(g.sum(0))
+        return dx, dw, db, None, None
+
+
+def _refuse_factored(weight) -> None:
+    if _factor_owner(weight) is not None:
+        raise RuntimeError(
+            "tdp.autocast: this Linear's weight has factored gradient synchronisation, which "
+            "replaces the weight-gradient GEMM the bf16 path computes itself; build the DDP with "
+            "DDP(factor_sync=False) to train under autocast")
+
+
 def _factor_owner(weight):
     """The DDP that factors ``weight``'s gradient synchronisation (it may gather the layer's
     input at forward time: DDP.factor_forward), else None."""
@@ -347,7 +445,18 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     # the input is the ReLU output of a previous fused Linear(+ReLU): this layer's input-gradient
     # epilogue applies that ReLU's mask (see _LinearFn.backward)
     gate_in = bool(getattr(x, "_tdp_relu_out", False)) and x.dim() == 2
+    amp = is_autocast_enabled() and x.dtype == torch.float32
     if not x.is_cuda:
+        if amp:
+            # the bf16 contract in torch math (with or without grad: the rounding is the point)
+            _refuse_factored(weight)
+            if torch.is_grad_enabled():
+                note_use(weight)
+            lead = x.shape[:-1]
+            y = _LinearBf16CpuFn.apply(x.reshape(-1, x.shape[-1]), weight, bias, relu, gate_in)
+            if relu and x.dim() == 2:
+                y._tdp_relu_out = True
+            return y if x.dim() == 2 else y.reshape(*lead, weight.shape[0])
         if torch.is_grad_enabled() and x.dtype == torch.float32:
             # the device op's gradient routing (arena slots, factored sync, hook order) in torch
             # math: the CPU/gloo tests see the same parameter-ready order as MI355X
@@ -366,8 +475,17 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     if x2.stride(-1) != 1:
         x2 = x2.contiguous()
         gate_in = False
+    if amp:
+        _refuse_factored(weight)
     if torch.is_grad_enabled():
         note_use(weight)
+    if amp:
+        y = _LinearBf16Fn.apply(x2, weight, bias, relu, gate_in)
+        if x.dim() == 2:
+            if relu:
+                y._tdp_relu_out = True
+            return y
+        return y.reshape(*lead, weight.shape[0])
     fac = _factor_owner(weight) if torch.is_grad_enabled() else None
     # the weight that produced x (a fused Linear+ReLU before this one): its g is this layer's
     # gated dx, whose gather this layer's backward can start (a tuple: not an autograd input)

@@ -188,8 +188,10 @@ def linear_cross_entropy(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tens
     small (out <= 16, batch <= 256, fp32); otherwise (and on CPU) exactly the two ops."""
     from .linear import _factor_owner, linear
     from ._grad import note_use
+    from .precision import is_autocast_enabled
 
-    fits = (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and weight.shape[0] <= 16 and
+    # under autocast the head is a bf16 Linear: the two ops, the loss itself in fp32
+    fits = (not is_autocast_enabled() and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and weight.shape[0] <= 16 and
             x.shape[0] <= 256 and x.shape[1] % 4 == 0 and reduction in ("mean", "sum") and
             weight.stride(1) == 1 and weight.stride(0) % 4 == 0 and weight.data_ptr() % 16 == 0 and
             x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and

@@ -4,7 +4,7 @@ Keys read by the reference: ``out_dir``, ``optional_args.{set_epoch, print_rand}
 ``local.condor.num_gpus`` (world size); ``script_path`` and ``local.condor.*`` by the submitter;
 ``local.device`` is dead config. Optional additions (absent -> reference values) live under
 ``train:`` -- model, batch sizes, epochs, checkpoint interval, optimizer, lr, bucket MiB,
-synthetic-data sizes, seed.
+synthetic-data sizes, seed, mixed precision.
 """
 from __future__ import annotations
 
@@ -35,7 +35,23 @@ TRAIN_DEFAULTS = {
     # bucket collectives overlap backward; "auto" = on a GPU (capture: with more than one rank)
     "fused_optimizer": "auto",
     "capture": "auto",
+    # no | bf16: Linear layers compute in bf16 mixed precision (tdp.autocast: bf16 operands, fp32
+    # accumulation, fp32 master weights and optimizer state); convolutions stay fp32
+    "mixed_precision": "no",
 }
+
+MIXED_PRECISION = ("no", "bf16")
+
+
+def mixed_precision_of(v) -> str:
+    """The ``train.mixed_precision`` value, validated (a bare YAML ``no`` parses as False)."""
+    if v is None or v is False:
+        return "no"
+    v = str(v).lower()
+    if v not in MIXED_PRECISION:
+        raise ValueError(f"train.mixed_precision: {v!r} is not supported; valid values are "
+                         f"{', '.join(MIXED_PRECISION)}")
+    return v
 
 
 def load_settings(path: str) -> dict:
@@ -45,6 +61,7 @@ def load_settings(path: str) -> dict:
     s.setdefault("local", {}).setdefault("condor", {})
     t = copy.deepcopy(TRAIN_DEFAULTS)
     t.update(s.get("train") or {})
+    t["mixed_precision"] = mixed_precision_of(t.get("mixed_precision"))
     s["train"] = t
     return s
 
