@@ -573,16 +573,28 @@ const float* hyper_ptr(const c10::optional<Tensor>& blk) {
   return blk->data_ptr<float>();
 }
 
+// A gradient / optimizer-state operand of `p`: the kernels index it like p through a raw float
+// pointer, so anything else (another device, dtype, layout or size) would be a device fault.
+void check_like(const Tensor& t, const Tensor& p, const char* what) {
+  TORCH_CHECK(t.defined(), what, " is undefined");
+  TORCH_CHECK(t.is_cuda() && t.device() == p.device(), what, " must be on the parameter's GPU");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, what, " must be float32");
+  TORCH_CHECK(t.is_contiguous(), what, " must be contiguous");
+  TORCH_CHECK(t.numel() == p.numel(), what, " must have the parameter's number of elements");
+}
+
 // `hyper` (optional device hyper block, kernels.h HyperSlot): the kernel reads lr / momentum /
 // betas / bias corrections / first-step flag / clip coefficient from it (graph-replay safe);
 // the by-value arguments then only carry the structural flags.
 void sgd_flat_op(Tensor& p, const Tensor& g, const c10::optional<Tensor>& buf, double lr,
                  double momentum, double dampening, double wd, bool nesterov, bool maximize,
                  bool first_step, double grad_scale, const c10::optional<Tensor>& hyper) {
-  CHECK_GPU(p); CHECK_F32(p); CHECK_CONTIG(p); CHECK_GPU(g); CHECK_F32(g); CHECK_CONTIG(g);
-  TORCH_CHECK(p.numel() == g.numel(), "sgd: p/g size mismatch");
-  if (momentum != 0.0)
-    TORCH_CHECK(buf.has_value() && buf->numel() == p.numel(), "sgd: momentum buffer required");
+  CHECK_GPU(p); CHECK_F32(p); CHECK_CONTIG(p);
+  check_like(g, p, "sgd: g");
+  if (momentum != 0.0) {
+    TORCH_CHECK(buf.has_value() && buf->defined(), "sgd: momentum buffer required");
+    check_like(*buf, p, "sgd: momentum buffer");
+  }
   SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, maximize,
              first_step, (float)grad_scale, hyper_ptr(hyper)};
   sgd_flat(p.data_ptr<float>(), g.data_ptr<float>(), fptr(buf), p.numel(), h, cur_stream());
@@ -593,9 +605,13 @@ void adam_flat_op(Tensor& p, const Tensor& g, Tensor& m, Tensor& v,
                   double wd, bool amsgrad, bool maximize, bool decoupled, int64_t step,
                   double grad_scale, const c10::optional<Tensor>& hyper) {
   CHECK_GPU(p); CHECK_F32(p); CHECK_CONTIG(p);
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(),
-              "adam: size mismatch");
-  if (amsgrad) TORCH_CHECK(vmax.has_value() && vmax->numel() == p.numel(), "adam: need vmax");
+  check_like(g, p, "adam: g");
+  check_like(m, p, "adam: m");
+  check_like(v, p, "adam: v");
+  if (amsgrad) {
+    TORCH_CHECK(vmax.has_value() && vmax->defined(), "adam: need vmax");
+    check_like(*vmax, p, "adam: vmax");
+  }
   AdamHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, amsgrad, maximize,
               decoupled, (float)(1.0 - std::pow(b1, (double)step)),
               (float)std::sqrt(1.0 - std::pow(b2, (double)step)), (float)grad_scale,
@@ -632,6 +648,13 @@ void clip_grad_norm_op(const std::vector<Tensor>& grads, Tensor& hyper, double m
   }
 }
 
+// One gradient / state tensor per parameter, each like its parameter (check_like).
+void check_list(const std::vector<Tensor>& ts, const std::vector<Tensor>& ps, const char* what) {
+  TORCH_CHECK(ts.size() == ps.size(), what, ": ", ts.size(), " tensors for ", ps.size(),
+              " parameters");
+  for (size_t i = 0; i < ps.size(); ++i) check_like(ts[i], ps[i], what);
+}
+
 // Build the chunk table (<= 64K elements per workgroup) on the host, ship it with the launch.
 Tensor chunk_table(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs,
                    const std::vector<Tensor>& s0, const std::vector<Tensor>& s1,
@@ -665,9 +688,11 @@ void sgd_multi_op(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs,
                   const c10::optional<Tensor>& hyper) {
   if (ps.empty()) return;
   for (auto& t : ps) { CHECK_GPU(t); CHECK_F32(t); CHECK_CONTIG(t); }
-  for (auto& t : gs) { CHECK_F32(t); CHECK_CONTIG(t); }
+  // every check precedes chunk_table: the table holds raw pointers the kernel writes through
+  check_list(gs, ps, "sgd_multi: gs");
+  if (momentum != 0.0) check_list(bufs, ps, "sgd_multi: bufs (momentum != 0)");
   int count = 0;
-  auto tab = chunk_table(ps, gs, bufs, {}, {}, &count);
+  auto tab = chunk_table(ps, gs, momentum != 0.0 ? bufs : std::vector<Tensor>{}, {}, {}, &count);
   SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, maximize,
              first_step, (float)grad_scale, hyper_ptr(hyper)};
   sgd_multi(reinterpret_cast<const TensorChunk*>(tab.data_ptr()), count, h, cur_stream());
@@ -680,6 +705,11 @@ void adam_multi_op(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs,
                    double grad_scale, const c10::optional<Tensor>& hyper) {
   if (ps.empty()) return;
   for (auto& t : ps) { CHECK_GPU(t); CHECK_F32(t); CHECK_CONTIG(t); }
+  // every check precedes chunk_table: the table holds raw pointers the kernel writes through
+  check_list(gs, ps, "adam_multi: gs");
+  check_list(ms, ps, "adam_multi: ms");
+  check_list(vs, ps, "adam_multi: vs");
+  if (amsgrad) check_list(vmaxs, ps, "adam_multi: vmaxs (amsgrad)");
   int count = 0;
   auto tab = chunk_table(ps, gs, ms, vs, amsgrad ? vmaxs : std::vector<Tensor>{}, &count);
   AdamHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, amsgrad, maximize,
@@ -1756,6 +1786,11 @@ float* block_ptr(const c10::optional<Tensor>& blk) {
   return const_cast<float*>(hyper_ptr(blk));
 }
 
+// Whether the last gemm_f32_sgd / gemm_f32_adam call ran wgrad_lockstep_kernel (plan.lockstep):
+// lockstep_ok falls back to the persistent kernel silently, a test has to be able to tell.
+bool g_epilogue_lockstep = false;
+bool gemm_f32_epilogue_lockstep() { return g_epilogue_lockstep; }
+
 // Weight-gradient GEMM whose epilogue applies SGD to explicit tensors (the tensor-sharded
 // wrapper's shards: their gradient is complete on this rank, no reduction precedes the update):
 // p / buf are C-shaped contiguous slices of the parameter and momentum arenas, the scalars come
@@ -1815,6 +1850,84 @@ bool gemm_f32_sgd_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig
   const GemmPlan plan = gemm_f32_plan(a, num_cus(C.get_device()));
   Tensor ws;
   if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options());
+  g_epilogue_lockstep = epi && plan.lockstep;
+  gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream());
+  return epi;
+}
+
+// The same for Adam / AdamW (gemm_f32_sgd_op line for line, kind = 2): p / m / v (/ vmax with
+// amsgrad) are C-shaped contiguous slices, the scalars and bias corrections come from the hyper
+// block (opt_step_begin(hyper, 2) before every step), amsgrad / maximize / decoupled are
+// structural. With rowsum and bias_p the bias is updated from the row sums by the same kernel.
+// Returns whether the epilogue ran; if not, C (and rowsum) hold the gradient as from gemm_f32.
+bool gemm_f32_adam_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, bool b_kcontig,
+                      const Tensor& p, const Tensor& m, const Tensor& v,
+                      const c10::optional<Tensor>& vmax, const Tensor& hyper, bool amsgrad,
+                      bool maximize, bool decoupled, const c10::optional<Tensor>& rowsum,
+                      const c10::optional<Tensor>& bias_p, const c10::optional<Tensor>& bias_m,
+                      const c10::optional<Tensor>& bias_v,
+                      const c10::optional<Tensor>& bias_vmax) {
+  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C); CHECK_GPU(p); CHECK_GPU(hyper);
+  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C); CHECK_F32(p);
+  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_CONTIG(C); CHECK_CONTIG(p);
+  const int M = (int)C.size(0), N = (int)C.size(1);
+  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
+  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
+  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
+  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
+  TORCH_CHECK(p.numel() == (int64_t)M * N, "gemm_f32_adam: p must have C's elements");
+  check_like(m, p, "gemm_f32_adam: m");
+  check_like(v, p, "gemm_f32_adam: v");
+  if (amsgrad) {
+    TORCH_CHECK(vmax.has_value() && vmax->defined(), "gemm_f32_adam: amsgrad needs vmax");
+    check_like(*vmax, p, "gemm_f32_adam: vmax");
+  }
+  TORCH_CHECK((int64_t)M * N < (int64_t)1 << 31, "gemm_f32_adam: parameter too large");
+  GemmF32Args a;
+  a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
+  a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = N;
+  a.M = M; a.N = N; a.K = K;
+  a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
+  if (rowsum.has_value() && rowsum->defined()) {
+    CHECK_GPU(*rowsum); CHECK_F32(*rowsum); CHECK_CONTIG(*rowsum);
+    TORCH_CHECK(rowsum->numel() == M, "gemm: rowsum must have M elements");
+    a.rowsum = rowsum->data_ptr<float>();
+  }
+  GemmF32Args probe = a;
+  probe.opt.kind = 2;
+  const GemmPlan pp = gemm_f32_plan(probe, num_cus(C.get_device()));
+  const bool epi = pp.fast && !pp.skinny && pp.splits == 1 && !a_kcontig && !b_kcontig;
+  if (epi) {
+    const AdamHyper h{0.f, 0.f, 0.f, 0.f, 0.f, amsgrad, maximize, decoupled, 1.f, 1.f, 1.f,
+                      block_ptr(hyper)};
+    a.opt.kind = 2;
+    a.opt.p = p.data_ptr<float>();
+    a.opt.s0 = m.data_ptr<float>();
+    a.opt.s1 = v.data_ptr<float>();
+    a.opt.s2 = amsgrad ? vmax->data_ptr<float>() : nullptr;
+    a.opt.adam = h;
+    if (a.rowsum != nullptr && bias_p.has_value() && bias_p->defined()) {
+      CHECK_GPU(*bias_p); CHECK_F32(*bias_p); CHECK_CONTIG(*bias_p);
+      TORCH_CHECK(bias_p->numel() == M, "gemm_f32_adam: the bias must have M elements");
+      TORCH_CHECK(bias_m.has_value() && bias_v.has_value(), "gemm_f32_adam: bias state");
+      check_like(*bias_m, *bias_p, "gemm_f32_adam: bias_m");
+      check_like(*bias_v, *bias_p, "gemm_f32_adam: bias_v");
+      if (amsgrad) {
+        TORCH_CHECK(bias_vmax.has_value() && bias_vmax->defined(),
+                    "gemm_f32_adam: amsgrad needs bias_vmax");
+        check_like(*bias_vmax, *bias_p, "gemm_f32_adam: bias_vmax");
+      }
+      a.bias_opt.kind = 2;
+      a.bias_opt.p = bias_p->data_ptr<float>();
+      a.bias_opt.s0 = bias_m->data_ptr<float>();
+      a.bias_opt.s1 = bias_v->data_ptr<float>();
+      a.bias_opt.s2 = amsgrad ? bias_vmax->data_ptr<float>() : nullptr;
+    }
+  }
+  const GemmPlan plan = gemm_f32_plan(a, num_cus(C.get_device()));
+  Tensor ws;
+  if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options());
+  g_epilogue_lockstep = epi && plan.lockstep;
   gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream());
   return epi;
 }
@@ -1851,6 +1964,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hyper"), py::arg("nesterov") = false, py::arg("maximize") = false,
         py::arg("rowsum") = py::none(), py::arg("bias_p") = py::none(),
         py::arg("bias_buf") = py::none());
+  m.def("gemm_f32_adam", &gemm_f32_adam_op, py::arg("A"), py::arg("B"), py::arg("C"),
+        py::arg("a_kcontig"), py::arg("b_kcontig"), py::arg("p"), py::arg("m"), py::arg("v"),
+        py::arg("vmax"), py::arg("hyper"), py::arg("amsgrad") = false,
+        py::arg("maximize") = false, py::arg("decoupled") = false,
+        py::arg("rowsum") = py::none(), py::arg("bias_p") = py::none(),
+        py::arg("bias_m") = py::none(), py::arg("bias_v") = py::none(),
+        py::arg("bias_vmax") = py::none());
   m.def("gemm_f32_plan", &gemm_f32_plan_op);
   m.def("gemm_planes", &gemm_planes_op, py::arg("Ap"), py::arg("B"), py::arg("C"),
         py::arg("b_kcontig"), py::arg("bias") = py::none(), py::arg("relu") = false,
@@ -1881,6 +2001,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_f32_set_lockstep", &gemm_f32_set_lockstep,
         "A/B: the lockstep weight-gradient + optimizer kernel (default off)");
   m.def("gemm_f32_lockstep", &gemm_f32_lockstep);
+  m.def("gemm_f32_epilogue_lockstep", &gemm_f32_epilogue_lockstep,
+        "whether the last gemm_f32_sgd / gemm_f32_adam call ran the lockstep kernel");
   m.def("relu_bias_bwd", &relu_bias_bwd_op, py::arg("dy"), py::arg("y") = py::none(),
         py::arg("db") = py::none(), py::arg("beta_db") = 0.0, py::arg("gscale") = 1.0);
   m.def("bias_act", &bias_act_op, py::arg("x"), py::arg("b"), py::arg("relu") = false);
