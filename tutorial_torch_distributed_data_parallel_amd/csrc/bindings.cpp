@@ -437,7 +437,7 @@ py::tuple head_bwd_op(const Tensor& g, const Tensor& x, const Tensor& w,
 
 // Head Linear + cross-entropy forward in one launch (planes.h head_ce). x [B, I] (B <= 256),
 // w [O, I] (O <= 16), labels [B] int64, ticket: 9 zeroed int32 scratch words (zero again after
-// the launch). Returns [loss, lse [B + 1], logits [B, O]] + with_grad: [dlogits (unit seed),
+// the launch). Returns [loss, lse [2B + 1], logits [B, O]] + with_grad: [dlogits (unit seed),
 // dx [B, I], planes of dx or an empty tensor]; an empty list when the shape is not supported.
 std::vector<Tensor> head_ce_op(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias,
                                const Tensor& labels, int64_t ignore_index, double smoothing,
@@ -472,7 +472,7 @@ std::vector<Tensor> head_ce_op(const Tensor& x, const Tensor& w, const c10::opti
     ldgate = gate->stride(0);
   }
   auto o = x.options();
-  Tensor loss = at::empty({}, o), lse = at::empty({B + 1}, o), logits = at::empty({B, O}, o);
+  Tensor loss = at::empty({}, o), lse = at::empty({2 * B + 1}, o), logits = at::empty({B, O}, o);
   Tensor rowbuf = at::empty({B, 4}, o);
   Tensor d, dx, pl;
   if (with_grad) {
@@ -522,7 +522,8 @@ std::vector<Tensor> ce_fwd_op(const Tensor& logits, const Tensor& labels, int64_
   const int B = (int)logits.size(0), C = (int)logits.size(1);
   TORCH_CHECK(labels.numel() == B, "labels must have one entry per row");
   auto loss = at::empty({}, logits.options());
-  auto lse = at::empty({B + 1}, logits.options());
+  // [lse per row | valid rows | lse rounding residual per row] (kernels.h cross_entropy_fwd)
+  auto lse = at::empty({2 * B + 1}, logits.options());
   float* accp = nullptr;
   if (acc.has_value() && acc->defined()) {
     CHECK_GPU(*acc); CHECK_F32(*acc);
@@ -548,7 +549,11 @@ Tensor ce_bwd_op(const Tensor& logits, const Tensor& labels, const Tensor& lse,
                  const Tensor& gout, int64_t ignore_index, double smoothing, bool mean) {
   CHECK_GPU(logits); CHECK_F32(logits); CHECK_ROWMAJOR(logits);
   CHECK_GPU(gout); CHECK_F32(gout);
+  CHECK_GPU(labels); CHECK_CONTIG(labels); CHECK_GPU(lse); CHECK_F32(lse); CHECK_CONTIG(lse);
+  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
   const int B = (int)logits.size(0), C = (int)logits.size(1);
+  TORCH_CHECK(labels.numel() == B, "labels must have one entry per row");
+  TORCH_CHECK(lse.numel() == 2 * (int64_t)B + 1, "ce_bwd: lse must be ce_fwd's [2B + 1] tensor");
   auto d = at::empty({B, C}, logits.options());
   auto g = gout.contiguous();
   cross_entropy_bwd(logits.data_ptr<float>(), labels.data_ptr<int64_t>(), lse.data_ptr<float>(),

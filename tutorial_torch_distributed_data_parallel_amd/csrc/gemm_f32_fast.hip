@@ -1062,8 +1062,13 @@ __device__ __forceinline__ void gemm_tile(const FastParams& p, const int lid, ld
     if (p.stats != nullptr && !split) {
       // Batch-norm statistics of this tile's columns, from the tile still in LDS (a convolution
       // whose output feeds a BatchNorm: the moments pass over the whole output is skipped).
-      // Shifted sums about the tile's first row keep the one-pass variance exact in practice
-      // (the deviations are O(std)); tiles merge with Chan's formula (bn_moments_partials).
+      // Shifted sums about the tile's first row keep the one-pass variance as good as a Welford
+      // pass PROVIDED the tile's first row lies within O(std) of the tile mean (then the
+      // deviations are O(std)); tiles merge with Chan's formula (bn_moments_partials). With an
+      // outlier in the shift row (1e3 std away) the merged statistics lose digits: measured
+      // relative to the largest channel, mean 8e-6 and variance 3e-5 against 2e-7 / 2e-7 of the
+      // Welford pass (docs/PARITY.md "numerical edge contracts";
+      // tests/test_hard_inputs_gpu.py::test_conv_epilogue_stats_outlier_shift_row pins it).
       const int lc = (threadIdx.x % C4) * 4;
       const f32x4 k4 = *reinterpret_cast<const f32x4*>(T + lc);
       f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};

@@ -380,7 +380,7 @@ struct HeadCeParams {
   const float* bias;
   const int64_t* labels;
   float* logits;   // [B][O]
-  float* lse;      // [B + 1]
+  float* lse;      // [2B + 1]: lse | valid rows | lse residual (kernels.h cross_entropy_fwd)
   float* rowbuf;   // [B][4] per-row loss / correct / valid
   unsigned* ticket;
   float* loss;
@@ -462,7 +462,10 @@ __global__ __launch_bounds__(256) void head_ce_kernel(HeadCeParams p) {
   if (threadIdx.x == 0) {
     const int64_t y = p.labels[row];
     const RowOut o = row_serial(lg, p.O, y, p.ignore_index, p.eps);
-    if (blockIdx.y == 0) p.lse[row] = o.lse;
+    if (blockIdx.y == 0) {
+      p.lse[row] = o.lse;
+      p.lse[p.B + 1 + row] = o.res;
+    }
     if (p.dpre) {
       const float g = p.mean ? 1.f / vd : 1.f;
       const bool ok = o.valid != 0.f;
@@ -471,7 +474,7 @@ __global__ __launch_bounds__(256) void head_ce_kernel(HeadCeParams p) {
       for (int c = 0; c < NMAX; ++c) {
         float v = 0.f;
         if (c < p.O && ok) {
-          const float pr = __expf(lg[c] - o.lse);
+          const float pr = ce_prob(lg[c], o.lse, o.res);
           v = g * (pr - (c == (int)y ? (1.f - p.eps) : 0.f) - p.eps / p.O);
         }
         d[c] = v;

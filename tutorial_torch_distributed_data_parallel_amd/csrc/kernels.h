@@ -208,7 +208,9 @@ void splitk_reduce(const float* ws, int splits, int M, int N, void* C, bool c_bf
 // Fused cross-entropy forward over logits[B,C] (fp32), int64 labels.
 //   out_loss[0] = mean (or sum) loss over non-ignored rows; also optional device accumulators:
 //   acc[0] += sum loss, acc[1] += #correct (argmax == label), acc[2] += #counted rows.
-//   lse_out[B] (optional) saves log-sum-exp per row for the backward.
+//   lse_out[2B + 1] (optional) is what the backward reads: [0, B) the log-sum-exp per row, [B]
+//   the mean's denominator (valid rows), [B + 1, 2B + 1) each row's rounding residual of the
+//   log-sum-exp (ce_row.h lse_split), so probabilities do not inherit ulp(|max logit|).
 void cross_entropy_fwd(const float* logits, const int64_t* labels, int B, int C, long ld,
                        int ignore_index, float label_smoothing, bool mean, float* out_loss,
                        float* lse_out, float* acc, hipStream_t s, float* dpre = nullptr);

@@ -39,10 +39,10 @@ __device__ RowOut row_wave(const float* x, int C, int64_t y, int ignore_index, f
   for (int c = lane; c < C; c += 64) se += __expf(x[c] - mx);
   se = wave_sum(se);
   RowOut o;
-  o.lse = mx + __logf(se);
+  lse_split(mx, __logf(se), o.lse, o.res);
   const bool valid = (y != ignore_index) && y >= 0 && y < C;
   o.valid = valid ? 1.f : 0.f;
-  o.loss = valid ? (o.lse - (1.f - eps) * x[y] - (eps / C) * sumx) : 0.f;
+  o.loss = valid ? ce_row_loss(o.lse, o.res, x[y], sumx, eps, C) : 0.f;
   o.correct = (valid && arg == (int)y) ? 1.f : 0.f;
   return o;
 }
@@ -62,12 +62,12 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
     // no second pass over the batch) -- ~half the latency of the general path
     __shared__ float red3[4][3];
     const int r = threadIdx.x;
-    RowOut o{0.f, 0.f, 0.f, 0.f};
+    RowOut o{0.f, 0.f, 0.f, 0.f, 0.f};
     int64_t y = ignore_index;
     if (r < B) {
       y = labels[r];
       o = row_serial(logits + (long)r * ld, C, y, ignore_index, eps);
-      if (lse) lse[r] = o.lse;
+      if (lse) { lse[r] = o.lse; lse[B + 1 + r] = o.res; }
     }
     ls = wave_sum(o.loss);
     cr = wave_sum(o.correct);
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
       for (int c = 0; c < C; ++c) {
         float v = 0.f;
         if (valid) {
-          const float pr = __expf(x[c] - o.lse);
+          const float pr = ce_prob(x[c], o.lse, o.res);
           v = g * (pr - (c == (int)y ? (1.f - eps) : 0.f) - eps / C);
         }
         dpre[r * C + c] = v;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
   if (C <= 32) {
     for (int r = threadIdx.x; r < B; r += 256) {
       const RowOut o = row_serial(logits + (long)r * ld, C, labels[r], ignore_index, eps);
-      if (lse) lse[r] = o.lse;
+      if (lse) { lse[r] = o.lse; lse[B + 1 + r] = o.res; }
       ls += o.loss; cr += o.correct; vd += o.valid;
     }
   } else {
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
     for (int r = wid; r < B; r += 4) {
       const RowOut o = row_wave(logits + (long)r * ld, C, labels[r], ignore_index, eps);
       if (lane == 0) {
-        if (lse) lse[r] = o.lse;
+        if (lse) { lse[r] = o.lse; lse[B + 1 + r] = o.res; }
         ls += o.loss; cr += o.correct; vd += o.valid;
       }
     }
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
       const bool valid = (y != ignore_index) && y >= 0 && y < C;
       float v = 0.f;
       if (valid) {
-        const float p = __expf(logits[(long)r * ld + c] - lse[r]);
+        const float p = ce_prob(logits[(long)r * ld + c], lse[r], lse[B + 1 + r]);
         v = g * (p - (c == (int)y ? (1.f - eps) : 0.f) - eps / C);
       }
       dpre[i] = v;
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
     const bool valid = (y != ignore_index) && y >= 0 && y < C;
     float v = 0.f;
     if (valid) {
-      const float p = __expf(logits[(long)r * ld + c] - lse[r]);
+      const float p = ce_prob(logits[(long)r * ld + c], lse[r], lse[B + 1 + r]);
       v = g * (p - (c == (int)y ? (1.f - eps) : 0.f) - eps / C);
     }
     d[(long)r * C + c] = v;

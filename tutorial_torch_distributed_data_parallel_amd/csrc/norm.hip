@@ -544,12 +544,16 @@ __global__ __launch_bounds__(256) void elemt_rows4(const float* __restrict__ x,
   if (rg >= RPW || c >= C) return;
   long b, e;
   range_of(N, splits, blockIdx.y, b, e);
-  float sc[4], sf[4];
+  // y = (x - mean) * sc + bias, centred first: folding the mean into a shift (x * sc + sf) rounds
+  // at |mean * sc|, which a large-mean / small-spread channel turns into an O(1) error, and a
+  // constant channel would not give exactly its bias
+  float sc[4], mn[4], sf[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float is = (eval || lm.stats) ? rsqrtf(invstd[c + j] + eps) : invstd[c + j];
     sc[j] = is * (w ? w[c + j] : 1.f);
-    sf[j] = (bb ? bb[c + j] : 0.f) - mean[c + j] * sc[j];
+    mn[j] = mean[c + j];
+    sf[j] = bb ? bb[c + j] : 0.f;
     if (lm.stats && blockIdx.y == 0 && rg == 0) {
       const float n = invstd[C];  // the local count (moments layout [mean | var | count])
       lm.stats[c + j] = mean[c + j];
@@ -575,7 +579,7 @@ __global__ __launch_bounds__(256) void elemt_rows4(const float* __restrict__ x,
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float q = fmaf(v[j], sc[j], sf[j]) + rv[j];
+      const float q = fmaf(v[j] - mn[j], sc[j], sf[j]) + rv[j];
       o[j] = relu ? fmaxf(q, 0.f) : q;
     }
     *reinterpret_cast<f32x4*>(y + r * C + c) = o;
@@ -588,7 +592,8 @@ __global__ __launch_bounds__(256) void elemt_rows4(const float* __restrict__ x,
   }
 }
 
-// dx = d*k1 + x*k2 + k3 (d = dy masked by y > 0), constants per channel
+// dx = d*k1 + (x - mean)*k2 + k3 (d = dy masked by y > 0), constants per channel; x is centred
+// before the multiply (x*k2 + mean-folded k3 cancels at |mean * k2| for a large-mean channel)
 __global__ __launch_bounds__(256) void bwd_elemt_rows4(
     const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ w,
@@ -603,7 +608,7 @@ __global__ __launch_bounds__(256) void bwd_elemt_rows4(
   long b, e;
   range_of(N, splits, blockIdx.y, b, e);
   const float inv_count = 1.f / cnt[0];
-  float k1[4], k2[4], k3[4];
+  float k1[4], k2[4], k3[4], mn[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float is = invstd[c + j];
@@ -613,7 +618,8 @@ __global__ __launch_bounds__(256) void bwd_elemt_rows4(
     const float q = is * is * mdyx;
     k1[j] = sw;
     k2[j] = -q * sw;
-    k3[j] = (mean[c + j] * q - mdy) * sw;
+    k3[j] = -mdy * sw;
+    mn[j] = mean[c + j];
   }
 #pragma unroll 4
   for (long r = b + rg; r < e; r += RPW) {
@@ -631,7 +637,7 @@ __global__ __launch_bounds__(256) void bwd_elemt_rows4(
     }
     f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = fmaf(d[j], k1[j], fmaf(xv[j], k2[j], k3[j]));
+    for (int j = 0; j < 4; ++j) o[j] = fmaf(d[j], k1[j], fmaf(xv[j] - mn[j], k2[j], k3[j]));
     *reinterpret_cast<f32x4*>(dx + off) = o;
     if (pl) store_planes4(pl + off, (long)N * C, o[0], o[1], o[2], o[3]);
     // gradient of the fused residual input: the ReLU-masked dy itself
@@ -740,7 +746,7 @@ __global__ __launch_bounds__(256) void bn1d_local_fwd_kernel(
   for (int j = 0; j < 4; ++j) {
     const float is = rsqrtf(var[j] + eps);
     sc[j] = is * (w ? w[c + j] : 1.f);
-    sf[j] = (bb ? bb[c + j] : 0.f) - mean[j] * sc[j];
+    sf[j] = bb ? bb[c + j] : 0.f;  // the bias alone: the element pass centres x (elemt_rows4)
     if (rg == 0) {
       stats[c + j] = mean[j];
       stats[C + c + j] = is;
@@ -764,7 +770,7 @@ __global__ __launch_bounds__(256) void bn1d_local_fwd_kernel(
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float t = fmaf(v[i][j], sc[j], sf[j]);
+      const float t = fmaf(v[i][j] - mean[j], sc[j], sf[j]);
       o[j] = relu ? fmaxf(t, 0.f) : t;
     }
     *reinterpret_cast<f32x4*>(y + (long)r * C + c) = o;
@@ -873,7 +879,7 @@ __global__ __launch_bounds__(256) void bn1d_local_bwd_kernel(
     const float qq = is * is * mdyx;
     k1[j] = sw;
     k2[j] = -qq * sw;
-    k3[j] = (mu[j] * qq - mdy) * sw;
+    k3[j] = -mdy * sw;
   }
   // dw / db are complete here. World size 1 + fused optimizer: the affine parameters are
   // updated in place (the optimizer's element update, as the weight-gradient GEMM epilogue does)
@@ -898,7 +904,8 @@ __global__ __launch_bounds__(256) void bn1d_local_bwd_kernel(
     if (r >= N) continue;
     f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = fmaf(d[i][j], k1[j], fmaf(xv[i][j], k2[j], k3[j]));
+    for (int j = 0; j < 4; ++j)
+      o[j] = fmaf(d[i][j], k1[j], fmaf(xv[i][j] - mu[j], k2[j], k3[j]));
     *reinterpret_cast<f32x4*>(dx + (long)r * C + c) = o;
     if (pl) store_planes4(pl + (long)r * C + c, (long)N * C, o[0], o[1], o[2], o[3]);
   }

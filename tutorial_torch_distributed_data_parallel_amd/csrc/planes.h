@@ -58,7 +58,7 @@ bool head_bwd(const float* g, long ldg, const float* x, long ldx, const float* w
               const OptEpilogue* wopt = nullptr, const OptEpilogue* bopt = nullptr);
 
 // Forward of a head Linear(I -> O <= 16) + cross-entropy in one launch (csrc/gemm_skinny.hip
-// head_ce_kernel, B <= 256 rows): logits [B][O], lse [B + 1] (lse[B] = valid rows), loss, the
+// head_ce_kernel, B <= 256 rows): logits [B][O], lse [2B + 1] (cross_entropy_fwd's layout), loss, the
 // metric accumulator acc [3] (optional); with dpre (training): the logits gradient for a unit
 // upstream gradient and, with dx, the input gradient dlogits . W (gated by gate > 0, planes into
 // dxp when given). rowbuf [B][4] scratch; ticket: 9 zeroed unsigned words, zero again afterwards.
