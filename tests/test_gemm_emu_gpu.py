@@ -1,5 +1,5 @@
-"""fp32 GEMM on the bf16 matrix core (exact 3-way bf16 split, six products: csrc/gemm_f32_fast.hip
-`split3_pair` / `mfma_emu6`) against a float64 reference, side by side with the native
+"""fp32 GEMM on the bf16 matrix core (exact 3-way bf16 split, six products: csrc/split_bf16.h
+`split3_bits` / `mfma_emu6`) against a float64 reference, side by side with the native
 v_mfma_f32_32x32x2_f32 path. The emulated path must carry fp32 accuracy: its error, measured
 against |A| @ |B| (the scale of the rounding error any fp32 summation order makes), stays within a
 small multiple of the native f32 MFMA path's error and within an absolute fp32 bound."""

@@ -468,3 +468,39 @@ def test_bn1d_sync_halves_match_the_split_path(Cn):
     torch.testing.assert_close(s1, s2, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(dw1, dw2, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(db1, db2, rtol=1e-4, atol=1e-4)
+
+
+# Every producer of planes against split_planes of its own fp32 output, bit for bit, at the
+# smallest shape its kernel takes (gemm_planes out_planes, head_bwd and gather_batch: above).
+def test_head_ce_planes_are_split_planes_of_dx(C):
+    from tutorial_torch_distributed_data_parallel_amd.ops.loss import _ticket
+
+    torch.manual_seed(5)
+    x = torch.relu(torch.randn(4, 64, device="cuda"))
+    w = torch.randn(10, 64, device="cuda")
+    b = torch.randn(10, device="cuda")
+    y = torch.randint(0, 10, (4,), device="cuda")
+    out = C.head_ce(x, w, b, y, -100, 0.0, True, None, with_grad=True, gate=x, planes=True,
+                    ticket=_ticket(x.device))
+    assert len(out) == 6, "head_ce takes B = 4, O = 10, I = 64"
+    dx, pl = out[4], out[5]
+    assert bool((dx != 0).any())
+    assert torch.equal(pl, C.split_planes(dx))
+
+
+def test_bn1d_planes_are_split_planes_of_their_output(C):
+    torch.manual_seed(6)
+    N, Cn = 4, 16
+    x = torch.randn(N, Cn, device="cuda") * 1.7 + 0.4
+    w, b = torch.randn(Cn, device="cuda"), torch.randn(Cn, device="cuda")
+    mk = torch.empty((N, Cn // 4), dtype=torch.uint8, device="cuda")
+    pl1, pl2, dpl = (torch.empty((3, N, Cn), dtype=torch.bfloat16, device="cuda")
+                     for _ in range(3))
+    r = C.bn1d_local_fwd(x, w, b, True, 1e-5, 0.1, mask_out=mk, planes_out=pl1)
+    assert r, "bn1d_local_fwd takes N <= 512 rows, C % 16 == 0"
+    y1, st = r
+    assert torch.equal(pl1, C.split_planes(y1))
+    y2, _ = C.bn_elemt_local(x, C.bn_moments(x)[0], w, b, True, 1e-5, 0.1, planes_out=pl2)
+    assert torch.equal(pl2, C.split_planes(y2))
+    dx = C.bn1d_local_bwd(torch.randn(N, Cn, device="cuda"), x, st, w, mask=mk, planes_out=dpl)
+    assert torch.equal(dpl, C.split_planes(dx))

@@ -44,79 +44,104 @@ float* fptr(const c10::optional<Tensor>& t) {
 }
 
 // --------------------------------------------------------------------------------------- GEMM
+// Optional contiguous fp32 GPU tensor of n elements -> its pointer, null when absent.
+float* opt_vec(const c10::optional<Tensor>& t, int64_t n, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(), what,
+              " must be a contiguous float32 GPU tensor");
+  TORCH_CHECK(t->numel() == n, what, " must have ", n, " elements");
+  return t->data_ptr<float>();
+}
+
+// Optional row-major fp32 GPU matrix [rows, cols] -> its pointer (null when absent) and leading
+// dimension.
+const float* opt_mat(const c10::optional<Tensor>& t, int64_t rows, int64_t cols, long* ld,
+                     const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->dim() == 2 &&
+                  t->stride(1) == 1, what, " must be a float32 GPU matrix with unit inner stride");
+  TORCH_CHECK(t->size(0) == rows && t->size(1) == cols, what, " must be [", rows, ", ", cols, "]");
+  *ld = t->stride(0);
+  return t->data_ptr<float>();
+}
+
+// B of C = A . op(B): fp32, [N, K] if b_kcontig else [K, N]
+void check_gemm_b(const Tensor& B, bool b_kcontig, int64_t N, int64_t K) {
+  CHECK_GPU(B); CHECK_F32(B); CHECK_ROWMAJOR(B);
+  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
+  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
+}
+
+// The operands of C = op(A) . op(B), checked:
 // A: [M,K] if a_kcontig else [K,M];  B: [N,K] if b_kcontig else [K,N];  C: [M,N]
+struct GemmDims {
+  int M, N, K;
+};
+GemmDims gemm_dims(const Tensor& A, const Tensor& B, const Tensor& C, bool a_kcontig,
+                   bool b_kcontig) {
+  CHECK_GPU(A); CHECK_GPU(C);
+  CHECK_F32(A); CHECK_F32(C);
+  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(C);
+  const int M = (int)C.size(0), N = (int)C.size(1);
+  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
+  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
+  check_gemm_b(B, b_kcontig, N, K);
+  return {M, N, K};
+}
+
+// The common part of GemmF32Args. c_contig: C must be contiguous, ldc = N (the optimizer
+// epilogues index the parameter like C).
+GemmF32Args gemm_f32_args(const Tensor& A, const Tensor& B, const Tensor& C, bool a_kcontig,
+                          bool b_kcontig, bool c_contig) {
+  const GemmDims d = gemm_dims(A, B, C, a_kcontig, b_kcontig);
+  if (c_contig) CHECK_CONTIG(C);
+  GemmF32Args a;
+  a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
+  a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = c_contig ? d.N : C.stride(0);
+  a.M = d.M; a.N = d.N; a.K = d.K;
+  a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
+  return a;
+}
+
+// allocates the plan's split-K workspace, if any, and runs
+void gemm_f32_launch(const GemmF32Args& a, const GemmPlan& plan, const Tensor& C, hipStream_t s) {
+  Tensor ws;
+  if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options());
+  gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, s);
+}
+
 void gemm_f32_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, bool b_kcontig,
                  const c10::optional<Tensor>& mask, const c10::optional<Tensor>& bias,
                  const c10::optional<Tensor>& rowsum, double beta, double rowsum_beta,
                  bool relu, const c10::optional<Tensor>& gate) {
-  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C);
-  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C);
-  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_ROWMAJOR(C);
-  const int M = (int)C.size(0), N = (int)C.size(1);
-  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
-  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
-  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
-  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
-  GemmF32Args a;
-  a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
-  a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = C.stride(0);
-  a.M = M; a.N = N; a.K = K;
-  a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
-  if (mask.has_value() && mask->defined()) {
-    CHECK_GPU(*mask); CHECK_F32(*mask); CHECK_ROWMAJOR(*mask);
-    TORCH_CHECK(mask->sizes() == A.sizes(), "gemm: mask must have A's shape");
-    a.mask = mask->data_ptr<float>();
-    a.ldmask = mask->stride(0);
-  }
-  if (bias.has_value() && bias->defined()) {
-    CHECK_GPU(*bias); CHECK_F32(*bias); CHECK_CONTIG(*bias);
-    TORCH_CHECK(bias->numel() == N, "gemm: bias must have N elements");
-    a.bias = bias->data_ptr<float>();
-  }
-  if (rowsum.has_value() && rowsum->defined()) {
-    CHECK_GPU(*rowsum); CHECK_F32(*rowsum); CHECK_CONTIG(*rowsum);
-    TORCH_CHECK(rowsum->numel() == M, "gemm: rowsum must have M elements");
-    a.rowsum = rowsum->data_ptr<float>();
-  }
+  GemmF32Args a = gemm_f32_args(A, B, C, a_kcontig, b_kcontig, false);
+  a.mask = opt_mat(mask, A.size(0), A.size(1), &a.ldmask, "gemm: mask (A's shape)");
+  a.bias = opt_vec(bias, a.N, "gemm: bias");
+  a.rowsum = opt_vec(rowsum, a.M, "gemm: rowsum");
   a.beta = (float)beta;
   a.rowsum_beta = (float)rowsum_beta;
   a.relu = relu;
-  bool gate_after = false;
-  if (gate.has_value() && gate->defined()) {
-    CHECK_GPU(*gate); CHECK_F32(*gate); CHECK_ROWMAJOR(*gate);
-    TORCH_CHECK(gate->size(0) == M && gate->size(1) == N, "gemm: gate must have C's shape");
-    a.gate = gate->data_ptr<float>();
-    a.ldgate = gate->stride(0);
-    // the fast kernel's row-vector epilogue reads the gate as 16-B rows
-    gate_after = (((uintptr_t)a.gate & 15) != 0 || a.ldgate % 4 != 0);
-  }
+  a.gate = opt_mat(gate, a.M, a.N, &a.ldgate, "gemm: gate (C's shape)");
+  // the fast kernel's row-vector epilogue reads the gate as 16-B rows
+  bool gate_after = a.gate && (((uintptr_t)a.gate & 15) != 0 || a.ldgate % 4 != 0);
   GemmPlan plan = gemm_f32_plan(a, num_cus(C.get_device()));
   const float* g = a.gate;
   if (gate_after && plan.fast) a.gate = nullptr;
   else gate_after = false;
-  Tensor ws;
-  if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options());
-  gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream());
-  if (gate_after) gate_inplace(a.C, a.ldc, g, gate->stride(0), M, N, cur_stream());
+  gemm_f32_launch(a, plan, C, cur_stream());
+  if (gate_after) gate_inplace(a.C, a.ldc, g, gate->stride(0), a.M, a.N, cur_stream());
 }
 
 // Mixed-precision GEMM (gemm_bf16.hip): fp32 tensors, operands rounded once to bf16, fp32
 // accumulation. Layouts as gemm_f32_op.
 GemmBf16Args gemm_bf16_args(const Tensor& A, const Tensor& B, const Tensor& C, bool a_kcontig,
                             bool b_kcontig) {
-  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C);
-  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C);
-  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_ROWMAJOR(C);
-  const int M = (int)C.size(0), N = (int)C.size(1);
-  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
-  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1, "gemm_bf16: empty operand");
-  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
-  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
-  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
+  const GemmDims d = gemm_dims(A, B, C, a_kcontig, b_kcontig);
+  TORCH_CHECK(d.M >= 1 && d.N >= 1 && d.K >= 1, "gemm_bf16: empty operand");
   GemmBf16Args a;
   a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
   a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = C.stride(0);
-  a.M = M; a.N = N; a.K = K;
+  a.M = d.M; a.N = d.N; a.K = d.K;
   a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
   a.num_cus = num_cus(C.get_device());
   return a;
@@ -127,22 +152,9 @@ void gemm_bf16_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, b
                   const c10::optional<Tensor>& rowsum, double beta) {
   GemmBf16Args a = gemm_bf16_args(A, B, C, a_kcontig, b_kcontig);
   TORCH_CHECK(beta == 0.0 || beta == 1.0, "gemm_bf16: beta must be 0 or 1");
-  if (bias.has_value() && bias->defined()) {
-    CHECK_GPU(*bias); CHECK_F32(*bias); CHECK_CONTIG(*bias);
-    TORCH_CHECK(bias->numel() == a.N, "gemm: bias must have N elements");
-    a.bias = bias->data_ptr<float>();
-  }
-  if (rowsum.has_value() && rowsum->defined()) {
-    CHECK_GPU(*rowsum); CHECK_F32(*rowsum); CHECK_CONTIG(*rowsum);
-    TORCH_CHECK(rowsum->numel() == a.M, "gemm: rowsum must have M elements");
-    a.rowsum = rowsum->data_ptr<float>();
-  }
-  if (gate.has_value() && gate->defined()) {
-    CHECK_GPU(*gate); CHECK_F32(*gate); CHECK_ROWMAJOR(*gate);
-    TORCH_CHECK(gate->size(0) == a.M && gate->size(1) == a.N, "gemm: gate must have C's shape");
-    a.gate = gate->data_ptr<float>();
-    a.ldgate = gate->stride(0);
-  }
+  a.bias = opt_vec(bias, a.N, "gemm_bf16: bias");
+  a.rowsum = opt_vec(rowsum, a.M, "gemm_bf16: rowsum");
+  a.gate = opt_mat(gate, a.M, a.N, &a.ldgate, "gemm_bf16: gate (C's shape)");
   a.beta = (float)beta;
   a.relu = relu;
   const GemmBf16Plan plan = gemm_bf16_plan(a, a.num_cus);
@@ -163,10 +175,30 @@ std::vector<int64_t> gemm_bf16_plan_op(const Tensor& A, const Tensor& B, const T
   return {plan.splits, plan.k_per_split, plan.guarded ? 1 : 0};
 }
 
-// Returns whether the epilogue ran. Weight-gradient GEMM whose epilogue applies the DDP's fused optimizer to arena elements
-// [offset, offset + M*N) instead of storing the gradient into C (world size 1, see
-// RcclBackend::epilogue_opt). C must be that contiguous arena slice (its contents are left as
-// they were: the gradient is never materialised).
+// A FusedOptimizer (the arena's parameter / state pointers and hyper-parameters) viewed at an
+// arena offset: the optimizer epilogue of the parameter that starts there.
+OptEpilogue epilogue_at(const FusedOptimizer& f, int64_t offset) {
+  OptEpilogue o;
+  o.kind = f.kind;
+  o.p = f.p + offset;
+  o.s0 = f.s0 ? f.s0 + offset : nullptr;
+  o.s1 = f.s1 ? f.s1 + offset : nullptr;
+  o.s2 = f.s2 ? f.s2 + offset : nullptr;
+  o.sgd = f.sgd;  // scalars: from the device hyper block (f.sgd.dev)
+  o.adam = f.adam;
+  return o;
+}
+
+// Whether a weight-gradient GEMM can run an optimizer epilogue of this kind: the epilogue exists
+// on the fast kernel's weight-gradient layout without split-K; any other plan stores the gradient
+// and leaves the update to the caller.
+bool wgrad_epilogue_ok(const GemmF32Args& a, int kind, int cus) {
+  GemmF32Args probe = a;
+  probe.opt.kind = kind;
+  const GemmPlan pp = gemm_f32_plan(probe, cus);
+  return pp.fast && !pp.skinny && pp.splits == 1 && !a.a_kcontig && !a.b_kcontig;
+}
+
 // The weight-gradient + optimizer GEMM behind SyncBackend::held_epilogue (gemm_f32_opt
 // hold=True): its arguments, plan and tensors until the next held call pairs with it
 // (gemm_f32_fast_run_pair) or the backend runs it alone at the end of backward.
@@ -181,58 +213,33 @@ struct HeldGemm {
 static std::shared_ptr<HeldGemm> g_held;
 static const SyncBackend* g_held_backend = nullptr;
 
+// Weight-gradient GEMM whose epilogue applies the DDP's fused optimizer to arena elements
+// [offset, offset + M*N) instead of storing the gradient into C (world size 1, see
+// RcclBackend::epilogue_opt). C must be that contiguous arena slice (its contents are left as
+// they were: the gradient is never materialised). Returns whether the epilogue ran; if not, C
+// holds the gradient and the update is left to the reducer's end-of-backward launch.
 bool gemm_f32_opt_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, bool b_kcontig,
                      SyncBackend& backend, int64_t offset, const c10::optional<Tensor>& rowsum,
                      double rowsum_beta, int64_t bias_offset, int64_t bias_span, bool hold) {
-  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C);
-  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C);
-  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_CONTIG(C);
-  const int M = (int)C.size(0), N = (int)C.size(1);
-  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
-  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
-  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
-  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
+  GemmF32Args a = gemm_f32_args(A, B, C, a_kcontig, b_kcontig, true);
+  const int M = a.M, N = a.N;
   TORCH_CHECK(backend.epilogue_allowed(), "optimizer epilogue: no fused optimizer at world 1");
   auto ops = std::dynamic_pointer_cast<RcclOps>(backend.ops());
   TORCH_CHECK(ops != nullptr, "optimizer epilogue needs the device (RCCL) backend");
-  GemmF32Args a;
-  a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
-  a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = N;
-  a.M = M; a.N = N; a.K = K;
-  a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
-  if (rowsum.has_value() && rowsum->defined()) {
-    CHECK_GPU(*rowsum); CHECK_F32(*rowsum); CHECK_CONTIG(*rowsum);
-    TORCH_CHECK(rowsum->numel() == M, "gemm: rowsum must have M elements");
-    a.rowsum = rowsum->data_ptr<float>();
-    a.rowsum_beta = (float)rowsum_beta;
-  }
+  a.rowsum = opt_vec(rowsum, M, "gemm: rowsum");
+  if (a.rowsum) a.rowsum_beta = (float)rowsum_beta;
   TORCH_CHECK((int64_t)M * N < (int64_t)1 << 31, "optimizer epilogue: parameter too large");
-  // the epilogue exists on the fast kernel's weight-gradient layout without split-K; any other
-  // plan stores the gradient and leaves the update to the reducer's end-of-backward launch
-  GemmF32Args probe = a;
-  probe.opt.kind = 1;
-  const GemmPlan pp = gemm_f32_plan(probe, num_cus(C.get_device()));
-  const bool epi = pp.fast && !pp.skinny && pp.splits == 1 && !a_kcontig && !b_kcontig;
+  const bool epi = wgrad_epilogue_ok(a, 1, num_cus(C.get_device()));
   if (epi) {
     const FusedOptimizer& f = ops->fused;
     backend.note_epilogue(offset, (int64_t)M * N);
-    a.opt.kind = f.kind;
-    a.opt.p = f.p + offset;
-    a.opt.s0 = f.s0 ? f.s0 + offset : nullptr;
-    a.opt.s1 = f.s1 ? f.s1 + offset : nullptr;
-    a.opt.s2 = f.s2 ? f.s2 + offset : nullptr;
-    a.opt.sgd = f.sgd;    // scalars: from the device hyper block (f.sgd.dev)
-    a.opt.adam = f.adam;
+    a.opt = epilogue_at(f, offset);
     if (bias_offset >= 0 && a.rowsum != nullptr && a.rowsum_beta == 0.f) {
       // the layer's bias [bias_offset, + M) is updated from the row sums by the same kernel;
       // its arena span (alignment padding included) is marked done for the reducer
       TORCH_CHECK(bias_span >= M, "optimizer epilogue: bias span shorter than the bias");
       backend.note_epilogue(bias_offset, bias_span);
-      a.bias_opt.kind = f.kind;
-      a.bias_opt.p = f.p + bias_offset;
-      a.bias_opt.s0 = f.s0 ? f.s0 + bias_offset : nullptr;
-      a.bias_opt.s1 = f.s1 ? f.s1 + bias_offset : nullptr;
-      a.bias_opt.s2 = f.s2 ? f.s2 + bias_offset : nullptr;
+      a.bias_opt = epilogue_at(f, bias_offset);
     }
   }
   const GemmPlan plan = gemm_f32_plan(a, num_cus(C.get_device()));
@@ -265,9 +272,7 @@ bool gemm_f32_opt_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig
       return epi;
     }
   }
-  Tensor ws;
-  if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options());
-  gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, s);
+  gemm_f32_launch(a, plan, C, s);
   return epi;
 }
 
@@ -277,14 +282,13 @@ bool gemm_f32_opt_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig
 void gemm_planes_op(const Tensor& Ap, const Tensor& B, Tensor& C, bool b_kcontig,
                     const c10::optional<Tensor>& bias, bool relu,
                     const c10::optional<Tensor>& gate, const c10::optional<Tensor>& out_planes) {
-  CHECK_GPU(Ap); CHECK_GPU(B); CHECK_GPU(C);
+  CHECK_GPU(Ap); CHECK_GPU(C);
   TORCH_CHECK(Ap.scalar_type() == at::kBFloat16 && Ap.dim() == 3 && Ap.size(0) == 3 &&
                   Ap.is_contiguous(), "gemm_planes: Ap must be a contiguous [3, M, K] bf16 tensor");
-  CHECK_F32(B); CHECK_F32(C); CHECK_ROWMAJOR(B); CHECK_ROWMAJOR(C);
+  CHECK_F32(C); CHECK_ROWMAJOR(C);
   const int M = (int)C.size(0), N = (int)C.size(1), K = (int)Ap.size(2);
   TORCH_CHECK(Ap.size(1) == M, "gemm_planes: A rows != C rows");
-  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm_planes: B cols != C cols");
-  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm_planes: inner dims differ");
+  check_gemm_b(B, b_kcontig, N, K);
   GemmPlanesArgs a;
   a.Ap = reinterpret_cast<const uint16_t*>(Ap.data_ptr());
   a.ps = Ap.stride(0); a.lda = Ap.stride(1);
@@ -292,17 +296,8 @@ void gemm_planes_op(const Tensor& Ap, const Tensor& B, Tensor& C, bool b_kcontig
   a.C = C.data_ptr<float>(); a.ldc = C.stride(0);
   a.M = M; a.N = N; a.K = K;
   a.relu = relu;
-  if (bias.has_value() && bias->defined()) {
-    CHECK_GPU(*bias); CHECK_F32(*bias); CHECK_CONTIG(*bias);
-    TORCH_CHECK(bias->numel() == N, "gemm_planes: bias must have N elements");
-    a.bias = bias->data_ptr<float>();
-  }
-  if (gate.has_value() && gate->defined()) {
-    CHECK_GPU(*gate); CHECK_F32(*gate); CHECK_ROWMAJOR(*gate);
-    TORCH_CHECK(gate->size(0) == M && gate->size(1) == N, "gemm_planes: gate must have C's shape");
-    a.gate = gate->data_ptr<float>();
-    a.ldgate = gate->stride(0);
-  }
+  a.bias = opt_vec(bias, N, "gemm_planes: bias");
+  a.gate = opt_mat(gate, M, N, &a.ldgate, "gemm_planes: gate (C's shape)");
   if (out_planes.has_value() && out_planes->defined()) {
     const Tensor& o = *out_planes;
     CHECK_GPU(o);
@@ -320,19 +315,13 @@ void gemm_planes_op(const Tensor& Ap, const Tensor& B, Tensor& C, bool b_kcontig
   gemm_planes_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream());
 }
 
-// x [rows, cols] fp32 (unit inner stride) -> its exact bf16 split planes [3, rows, cols]
 // large-tile split-bf16 GEMM (csrc/gemm_emu8.hip): A [M,K]; B [N,K] if b_kcontig else [K,N]
 void gemm_emu8_op(const Tensor& A, const Tensor& B, Tensor& C, bool b_kcontig, double beta) {
-  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C);
-  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C);
-  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_ROWMAJOR(C);
+  const GemmDims d = gemm_dims(A, B, C, true, b_kcontig);
   GemmEmu8Args a;
-  a.M = (int)C.size(0);
-  a.N = (int)C.size(1);
-  a.K = (int)A.size(1);
-  TORCH_CHECK(A.size(0) == a.M, "gemm_emu8: A rows != C rows");
-  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == a.N, "gemm_emu8: B cols != C cols");
-  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == a.K, "gemm_emu8: inner dims differ");
+  a.M = d.M;
+  a.N = d.N;
+  a.K = d.K;
   a.A = A.data_ptr<float>();
   a.B = B.data_ptr<float>();
   a.C = C.data_ptr<float>();
@@ -345,6 +334,7 @@ void gemm_emu8_op(const Tensor& A, const Tensor& B, Tensor& C, bool b_kcontig, d
   gemm_emu8_run(a, cur_stream());
 }
 
+// x [rows, cols] fp32 (unit inner stride) -> its exact bf16 split planes [3, rows, cols]
 Tensor split_planes_op(const Tensor& x) {
   CHECK_GPU(x); CHECK_F32(x); CHECK_ROWMAJOR(x);
   const int rows = (int)x.size(0), cols = (int)x.size(1);
@@ -380,20 +370,9 @@ py::tuple head_bwd_op(const Tensor& g, const Tensor& x, const Tensor& w,
     TORCH_CHECK(dx.size(0) == B && dx.size(1) == I, "head_bwd: dx shape mismatch");
   }
   planes = planes && has_dx;
-  float* dbp = nullptr;
-  if (db.has_value() && db->defined()) {
-    CHECK_GPU(*db); CHECK_F32(*db); CHECK_CONTIG(*db);
-    TORCH_CHECK(db->numel() == O, "head_bwd: db must have O elements");
-    dbp = db->data_ptr<float>();
-  }
-  const float* gp = nullptr;
+  float* dbp = opt_vec(db, O, "head_bwd: db");
   long ldgate = 0;
-  if (gate.has_value() && gate->defined()) {
-    CHECK_GPU(*gate); CHECK_F32(*gate); CHECK_ROWMAJOR(*gate);
-    TORCH_CHECK(gate->size(0) == B && gate->size(1) == I, "head_bwd: gate must have dx's shape");
-    gp = gate->data_ptr<float>();
-    ldgate = gate->stride(0);
-  }
+  const float* gp = opt_mat(gate, B, I, &ldgate, "head_bwd: gate (dx's shape)");
   Tensor pl;
   if (planes) pl = at::empty({3, (long)B, (long)I}, dx.options().dtype(at::kBFloat16));
   // world size 1 + fused optimizer (backend given): W and b are updated by the kernel instead of
@@ -404,22 +383,10 @@ py::tuple head_bwd_op(const Tensor& g, const Tensor& x, const Tensor& w,
     auto ops = std::dynamic_pointer_cast<RcclOps>(backend->ops());
     TORCH_CHECK(ops != nullptr, "head_bwd: optimizer epilogue needs the device backend");
     TORCH_CHECK(dw.is_contiguous(), "head_bwd: dw must be the contiguous arena slot");
-    const FusedOptimizer& f = ops->fused;
-    auto at_off = [&](int64_t off) {
-      OptEpilogue o;
-      o.kind = f.kind;
-      o.p = f.p + off;
-      o.s0 = f.s0 ? f.s0 + off : nullptr;
-      o.s1 = f.s1 ? f.s1 + off : nullptr;
-      o.s2 = f.s2 ? f.s2 + off : nullptr;
-      o.sgd = f.sgd;
-      o.adam = f.adam;
-      return o;
-    };
-    wo = at_off(w_offset);
+    wo = epilogue_at(ops->fused, w_offset);
     if (dbp != nullptr && b_offset >= 0) {
       TORCH_CHECK(b_span >= O, "head_bwd: bias span shorter than the bias");
-      bo = at_off(b_offset);
+      bo = epilogue_at(ops->fused, b_offset);
     }
   }
   const bool ok = head_bwd(g.data_ptr<float>(), g.stride(0), x.data_ptr<float>(), x.stride(0),
@@ -451,26 +418,15 @@ std::vector<Tensor> head_ce_op(const Tensor& x, const Tensor& w, const c10::opti
   TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() >= 9, "ticket: 9 int32 words");
   const int B = (int)x.size(0), I = (int)x.size(1), O = (int)w.size(0);
   TORCH_CHECK(w.size(1) == I && labels.numel() == B, "head_ce: shape mismatch");
-  const float* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    CHECK_GPU(*bias); CHECK_F32(*bias); CHECK_CONTIG(*bias);
-    TORCH_CHECK(bias->numel() == O, "head_ce: bias must have O elements");
-    bp = bias->data_ptr<float>();
-  }
+  const float* bp = opt_vec(bias, O, "head_ce: bias");
   float* accp = nullptr;
   if (acc.has_value() && acc->defined()) {
     CHECK_GPU(*acc); CHECK_F32(*acc);
     TORCH_CHECK(acc->numel() >= 3, "acc needs 3 floats");
     accp = acc->data_ptr<float>();
   }
-  const float* gp = nullptr;
   long ldgate = 0;
-  if (gate.has_value() && gate->defined()) {
-    CHECK_GPU(*gate); CHECK_F32(*gate); CHECK_ROWMAJOR(*gate);
-    TORCH_CHECK(gate->size(0) == B && gate->size(1) == I, "head_ce: gate must have x's shape");
-    gp = gate->data_ptr<float>();
-    ldgate = gate->stride(0);
-  }
+  const float* gp = opt_mat(gate, B, I, &ldgate, "head_ce: gate (x's shape)");
   auto o = x.options();
   Tensor loss = at::empty({}, o), lse = at::empty({2 * B + 1}, o), logits = at::empty({B, O}, o);
   Tensor rowbuf = at::empty({B, 4}, o);
@@ -1008,26 +964,15 @@ Tensor bn1d_local_bwd_op(const Tensor& dy, const Tensor& x, const Tensor& stats,
     auto ops = std::dynamic_pointer_cast<RcclOps>(backend->ops());
     TORCH_CHECK(ops != nullptr, "bn1d_local_bwd: optimizer epilogue needs the device backend");
     const FusedOptimizer& f = ops->fused;
-    auto at_off = [&](int64_t off) {
-      OptEpilogue o;
-      o.kind = f.kind;
-      o.p = f.p + off;
-      o.s0 = f.s0 ? f.s0 + off : nullptr;
-      o.s1 = f.s1 ? f.s1 + off : nullptr;
-      o.s2 = f.s2 ? f.s2 + off : nullptr;
-      o.sgd = f.sgd;
-      o.adam = f.adam;
-      return o;
-    };
     if (w_offset >= 0) {
       TORCH_CHECK(w_span >= C && w.has_value() && w->defined() &&
                       w->data_ptr<float>() == f.p + w_offset,
                   "bn1d_local_bwd: w must be the arena parameter at w_offset");
-      wo = at_off(w_offset);
+      wo = epilogue_at(f, w_offset);
     }
     if (b_offset >= 0) {
       TORCH_CHECK(b_span >= C, "bn1d_local_bwd: bias span shorter than the bias");
-      bo = at_off(b_offset);
+      bo = epilogue_at(f, b_offset);
     }
   }
   auto dx = at::empty_like(x);
@@ -1796,6 +1741,36 @@ float* block_ptr(const c10::optional<Tensor>& blk) {
 bool g_epilogue_lockstep = false;
 bool gemm_f32_epilogue_lockstep() { return g_epilogue_lockstep; }
 
+// What gemm_f32_sgd / gemm_f32_adam share on the way in: the GEMM operands (C contiguous), the
+// C-shaped contiguous parameter slice p, the hyper block and the optional row sums.
+GemmF32Args wgrad_opt_args(const Tensor& A, const Tensor& B, const Tensor& C, bool a_kcontig,
+                           bool b_kcontig, const Tensor& p, const Tensor& hyper,
+                           const c10::optional<Tensor>& rowsum, const char* op) {
+  GemmF32Args a = gemm_f32_args(A, B, C, a_kcontig, b_kcontig, true);
+  CHECK_GPU(p); CHECK_GPU(hyper); CHECK_F32(p); CHECK_CONTIG(p);
+  TORCH_CHECK(p.numel() == (int64_t)a.M * a.N, op, ": p must have C's elements");
+  TORCH_CHECK((int64_t)a.M * a.N < (int64_t)1 << 31, op, ": parameter too large");
+  a.rowsum = opt_vec(rowsum, a.M, "gemm: rowsum");
+  return a;
+}
+
+// ... and on the way out: with a plan that has the epilogue (wgrad_epilogue_ok) the weight's
+// update rides on the GEMM -- and, when there are row sums and a bias epilogue (bopt.kind != 0),
+// the bias's; otherwise the plain GEMM runs. Returns whether the epilogue ran.
+bool wgrad_opt_run(GemmF32Args a, const Tensor& C, const OptEpilogue& wopt,
+                   const OptEpilogue& bopt) {
+  const int cus = num_cus(C.get_device());
+  const bool epi = wgrad_epilogue_ok(a, wopt.kind, cus);
+  if (epi) {
+    a.opt = wopt;
+    if (a.rowsum != nullptr) a.bias_opt = bopt;
+  }
+  const GemmPlan plan = gemm_f32_plan(a, cus);
+  g_epilogue_lockstep = epi && plan.lockstep;
+  gemm_f32_launch(a, plan, C, cur_stream());
+  return epi;
+}
+
 // Weight-gradient GEMM whose epilogue applies SGD to explicit tensors (the tensor-sharded
 // wrapper's shards: their gradient is complete on this rank, no reduction precedes the update):
 // p / buf are C-shaped contiguous slices of the parameter and momentum arenas, the scalars come
@@ -1806,65 +1781,31 @@ bool gemm_f32_sgd_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig
                      const Tensor& p, const c10::optional<Tensor>& buf, const Tensor& hyper,
                      bool nesterov, bool maximize, const c10::optional<Tensor>& rowsum,
                      const c10::optional<Tensor>& bias_p, const c10::optional<Tensor>& bias_buf) {
-  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C); CHECK_GPU(p); CHECK_GPU(hyper);
-  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C); CHECK_F32(p);
-  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_CONTIG(C); CHECK_CONTIG(p);
-  const int M = (int)C.size(0), N = (int)C.size(1);
-  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
-  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
-  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
-  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
-  TORCH_CHECK(p.numel() == (int64_t)M * N, "gemm_f32_sgd: p must have C's elements");
+  const GemmF32Args a =
+      wgrad_opt_args(A, B, C, a_kcontig, b_kcontig, p, hyper, rowsum, "gemm_f32_sgd");
   const bool mom = buf.has_value() && buf->defined();
-  if (mom) {
-    CHECK_GPU(*buf); CHECK_F32(*buf); CHECK_CONTIG(*buf);
-    TORCH_CHECK(buf->numel() == p.numel(), "gemm_f32_sgd: momentum buffer size");
-  }
-  TORCH_CHECK((int64_t)M * N < (int64_t)1 << 31, "gemm_f32_sgd: parameter too large");
-  GemmF32Args a;
-  a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
-  a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = N;
-  a.M = M; a.N = N; a.K = K;
-  a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
-  if (rowsum.has_value() && rowsum->defined()) {
-    CHECK_GPU(*rowsum); CHECK_F32(*rowsum); CHECK_CONTIG(*rowsum);
-    TORCH_CHECK(rowsum->numel() == M, "gemm: rowsum must have M elements");
-    a.rowsum = rowsum->data_ptr<float>();
-  }
-  GemmF32Args probe = a;
-  probe.opt.kind = 1;
-  const GemmPlan pp = gemm_f32_plan(probe, num_cus(C.get_device()));
-  const bool epi = pp.fast && !pp.skinny && pp.splits == 1 && !a_kcontig && !b_kcontig;
-  if (epi) {
-    const SgdHyper h{0.f, mom ? 1.f : 0.f, 0.f, 0.f, nesterov, maximize, false, 1.f,
-                     block_ptr(hyper)};
-    a.opt.kind = 1;
-    a.opt.p = p.data_ptr<float>();
-    a.opt.s0 = mom ? buf->data_ptr<float>() : nullptr;
-    a.opt.sgd = h;
-    if (a.rowsum != nullptr && bias_p.has_value() && bias_p->defined()) {
-      CHECK_GPU(*bias_p); CHECK_F32(*bias_p); CHECK_CONTIG(*bias_p);
-      TORCH_CHECK(bias_p->numel() == M, "gemm_f32_sgd: the bias must have M elements");
-      TORCH_CHECK(!mom || (bias_buf.has_value() && bias_buf->defined() &&
-                           bias_buf->numel() == M), "gemm_f32_sgd: bias momentum buffer");
-      a.bias_opt.kind = 1;
-      a.bias_opt.p = bias_p->data_ptr<float>();
-      a.bias_opt.s0 = mom ? bias_buf->data_ptr<float>() : nullptr;
+  if (mom) check_like(*buf, p, "gemm_f32_sgd: momentum buffer");
+  OptEpilogue wo, bo;
+  wo.kind = 1;
+  wo.p = p.data_ptr<float>();
+  wo.s0 = mom ? buf->data_ptr<float>() : nullptr;
+  wo.sgd = SgdHyper{0.f, mom ? 1.f : 0.f, 0.f, 0.f, nesterov, maximize, false, 1.f,
+                    block_ptr(hyper)};
+  if (a.rowsum != nullptr && bias_p.has_value() && bias_p->defined()) {
+    bo.kind = 1;
+    bo.p = opt_vec(bias_p, a.M, "gemm_f32_sgd: the bias");
+    if (mom) {
+      TORCH_CHECK(bias_buf.has_value(), "gemm_f32_sgd: bias momentum buffer");
+      check_like(*bias_buf, *bias_p, "gemm_f32_sgd: bias momentum buffer");
+      bo.s0 = bias_buf->data_ptr<float>();
     }
   }
-  const GemmPlan plan = gemm_f32_plan(a, num_cus(C.get_device()));
-  Tensor ws;
-  if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options());
-  g_epilogue_lockstep = epi && plan.lockstep;
-  gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream());
-  return epi;
+  return wgrad_opt_run(a, C, wo, bo);
 }
 
-// The same for Adam / AdamW (gemm_f32_sgd_op line for line, kind = 2): p / m / v (/ vmax with
-// amsgrad) are C-shaped contiguous slices, the scalars and bias corrections come from the hyper
-// block (opt_step_begin(hyper, 2) before every step), amsgrad / maximize / decoupled are
-// structural. With rowsum and bias_p the bias is updated from the row sums by the same kernel.
-// Returns whether the epilogue ran; if not, C (and rowsum) hold the gradient as from gemm_f32.
+// The same for Adam / AdamW: p / m / v (/ vmax with amsgrad) are C-shaped contiguous slices, the
+// scalars and bias corrections come from the hyper block (opt_step_begin(hyper, 2) before every
+// step), amsgrad / maximize / decoupled are structural.
 bool gemm_f32_adam_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, bool b_kcontig,
                       const Tensor& p, const Tensor& m, const Tensor& v,
                       const c10::optional<Tensor>& vmax, const Tensor& hyper, bool amsgrad,
@@ -1872,69 +1813,33 @@ bool gemm_f32_adam_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kconti
                       const c10::optional<Tensor>& bias_p, const c10::optional<Tensor>& bias_m,
                       const c10::optional<Tensor>& bias_v,
                       const c10::optional<Tensor>& bias_vmax) {
-  CHECK_GPU(A); CHECK_GPU(B); CHECK_GPU(C); CHECK_GPU(p); CHECK_GPU(hyper);
-  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C); CHECK_F32(p);
-  CHECK_ROWMAJOR(A); CHECK_ROWMAJOR(B); CHECK_CONTIG(C); CHECK_CONTIG(p);
-  const int M = (int)C.size(0), N = (int)C.size(1);
-  const int K = (int)(a_kcontig ? A.size(1) : A.size(0));
-  TORCH_CHECK((a_kcontig ? A.size(0) : A.size(1)) == M, "gemm: A rows != C rows");
-  TORCH_CHECK((b_kcontig ? B.size(0) : B.size(1)) == N, "gemm: B cols != C cols");
-  TORCH_CHECK((b_kcontig ? B.size(1) : B.size(0)) == K, "gemm: inner dims differ");
-  TORCH_CHECK(p.numel() == (int64_t)M * N, "gemm_f32_adam: p must have C's elements");
-  check_like(m, p, "gemm_f32_adam: m");
-  check_like(v, p, "gemm_f32_adam: v");
-  if (amsgrad) {
-    TORCH_CHECK(vmax.has_value() && vmax->defined(), "gemm_f32_adam: amsgrad needs vmax");
-    check_like(*vmax, p, "gemm_f32_adam: vmax");
-  }
-  TORCH_CHECK((int64_t)M * N < (int64_t)1 << 31, "gemm_f32_adam: parameter too large");
-  GemmF32Args a;
-  a.A = A.data_ptr<float>(); a.B = B.data_ptr<float>(); a.C = C.data_ptr<float>();
-  a.lda = A.stride(0); a.ldb = B.stride(0); a.ldc = N;
-  a.M = M; a.N = N; a.K = K;
-  a.a_kcontig = a_kcontig; a.b_kcontig = b_kcontig;
-  if (rowsum.has_value() && rowsum->defined()) {
-    CHECK_GPU(*rowsum); CHECK_F32(*rowsum); CHECK_CONTIG(*rowsum);
-    TORCH_CHECK(rowsum->numel() == M, "gemm: rowsum must have M elements");
-    a.rowsum = rowsum->data_ptr<float>();
-  }
-  GemmF32Args probe = a;
-  probe.opt.kind = 2;
-  const GemmPlan pp = gemm_f32_plan(probe, num_cus(C.get_device()));
-  const bool epi = pp.fast && !pp.skinny && pp.splits == 1 && !a_kcontig && !b_kcontig;
-  if (epi) {
-    const AdamHyper h{0.f, 0.f, 0.f, 0.f, 0.f, amsgrad, maximize, decoupled, 1.f, 1.f, 1.f,
+  const GemmF32Args a =
+      wgrad_opt_args(A, B, C, a_kcontig, b_kcontig, p, hyper, rowsum, "gemm_f32_adam");
+  // the Adam epilogue of a parameter: m, v and (amsgrad) vmax, each like it (check_like)
+  auto adam_of = [amsgrad](const Tensor& par, const c10::optional<Tensor>& m,
+                           const c10::optional<Tensor>& v, const c10::optional<Tensor>& vmax,
+                           const char* what) {
+    TORCH_CHECK(m.has_value() && v.has_value() && (!amsgrad || vmax.has_value()), what,
+                ": m, v (amsgrad: vmax) required");
+    check_like(*m, par, what);
+    check_like(*v, par, what);
+    if (amsgrad) check_like(*vmax, par, what);
+    OptEpilogue o;
+    o.kind = 2;
+    o.p = par.data_ptr<float>();
+    o.s0 = m->data_ptr<float>();
+    o.s1 = v->data_ptr<float>();
+    o.s2 = amsgrad ? vmax->data_ptr<float>() : nullptr;
+    return o;
+  };
+  OptEpilogue wo = adam_of(p, m, v, vmax, "gemm_f32_adam: state"), bo;
+  wo.adam = AdamHyper{0.f, 0.f, 0.f, 0.f, 0.f, amsgrad, maximize, decoupled, 1.f, 1.f, 1.f,
                       block_ptr(hyper)};
-    a.opt.kind = 2;
-    a.opt.p = p.data_ptr<float>();
-    a.opt.s0 = m.data_ptr<float>();
-    a.opt.s1 = v.data_ptr<float>();
-    a.opt.s2 = amsgrad ? vmax->data_ptr<float>() : nullptr;
-    a.opt.adam = h;
-    if (a.rowsum != nullptr && bias_p.has_value() && bias_p->defined()) {
-      CHECK_GPU(*bias_p); CHECK_F32(*bias_p); CHECK_CONTIG(*bias_p);
-      TORCH_CHECK(bias_p->numel() == M, "gemm_f32_adam: the bias must have M elements");
-      TORCH_CHECK(bias_m.has_value() && bias_v.has_value(), "gemm_f32_adam: bias state");
-      check_like(*bias_m, *bias_p, "gemm_f32_adam: bias_m");
-      check_like(*bias_v, *bias_p, "gemm_f32_adam: bias_v");
-      if (amsgrad) {
-        TORCH_CHECK(bias_vmax.has_value() && bias_vmax->defined(),
-                    "gemm_f32_adam: amsgrad needs bias_vmax");
-        check_like(*bias_vmax, *bias_p, "gemm_f32_adam: bias_vmax");
-      }
-      a.bias_opt.kind = 2;
-      a.bias_opt.p = bias_p->data_ptr<float>();
-      a.bias_opt.s0 = bias_m->data_ptr<float>();
-      a.bias_opt.s1 = bias_v->data_ptr<float>();
-      a.bias_opt.s2 = amsgrad ? bias_vmax->data_ptr<float>() : nullptr;
-    }
+  if (a.rowsum != nullptr && bias_p.has_value() && bias_p->defined()) {
+    opt_vec(bias_p, a.M, "gemm_f32_adam: the bias");
+    bo = adam_of(*bias_p, bias_m, bias_v, bias_vmax, "gemm_f32_adam: bias state");
   }
-  const GemmPlan plan = gemm_f32_plan(a, num_cus(C.get_device()));
-  Tensor ws;
-  if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options());
-  g_epilogue_lockstep = epi && plan.lockstep;
-  gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream());
-  return epi;
+  return wgrad_opt_run(a, C, wo, bo);
 }
 
 }  // namespace

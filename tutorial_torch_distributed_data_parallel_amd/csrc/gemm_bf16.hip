@@ -2,7 +2,7 @@
 //
 // The autocast path of ops/linear.py. Operands and output live in memory as fp32; every operand
 // element is rounded ONCE to bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32 -- the conversion
-// split3_pair uses for its head term) and the products run as ONE v_mfma_f32_32x32x16_bf16 per
+// split3_bits uses for its head term) and the products run as ONE v_mfma_f32_32x32x16_bf16 per
 // 16-deep K step: one of the six products of the split-bf16 fp32 GEMM (gemm_f32_fast.hip) and none
 // of its VALU split. The products of two bf16 values are exact in fp32, so the only error beyond
 // the operand rounding is the fp32 accumulation.
@@ -33,6 +33,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "split_bf16.h"  // the vector typedefs
 
 namespace tdp {
 namespace {
@@ -43,11 +44,6 @@ constexpr int kRowB = kBK * 2;          // LDS row: 64 bf16
 constexpr int kOpB = kBM * kRowB;       // 16 KiB per operand tile
 constexpr int kStageB = 2 * kOpB;       // A + B
 constexpr int kLdsB = 2 * kStageB;      // two stages
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct BParams {
   const float* A;

@@ -18,7 +18,7 @@
 //     interleaved columns 2i + g);
 //   * fragments use the fast kernel's k permutation (lane half h holds k = 16j + 4h + s and
 //     16j + 8 + 4h + s of K16 step j, the same for A and B) and its exact three-term split with
-//     the six kept products (split3 / mfma6 below: the same instruction sequence).
+//     the six kept products (split_bf16.h).
 // Measured against the fast kernel: profiles/r9/gemm_emu8_r9.md.
 #include <algorithm>
 #include <stdexcept>
@@ -26,6 +26,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "emu8.h"
+#include "split_bf16.h"
 
 namespace tdp {
 namespace {
@@ -35,12 +36,6 @@ constexpr int kTile = 256;
 constexpr int kImg = kTile * kBK8 * 4;  // 32 KiB per operand per stage
 constexpr int kStage = 2 * kImg;
 constexpr int kStages = 2;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef char lds_char;
 
 struct E8Params {
   const float* A;
@@ -54,51 +49,9 @@ struct E8Params {
   int relu;
 };
 
-__device__ __forceinline__ void split_pair8(float x0, float x1, unsigned& h, unsigned& m,
-                                            unsigned& l) {
-  const unsigned hu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf2));
-  const float r0 = x0 - __uint_as_float(hu << 16), r1 = x1 - __uint_as_float(hu & 0xffff0000u);
-  const unsigned mu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf2));
-  const float s0 = r0 - __uint_as_float(mu << 16), s1 = r1 - __uint_as_float(mu & 0xffff0000u);
-  h = hu;
-  m = mu;
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf2));
-}
-
-struct Planes {
+struct Planes {  // one fragment's three MFMA operands (split_bf16.h split3_x8)
   bf8 h, m, l;
 };
-
-__device__ __forceinline__ Planes split8(const f32x4& x0, const f32x4& x1) {
-  unsigned hs[4], ms[4], ls[4];
-  split_pair8(x0[0], x0[1], hs[0], ms[0], ls[0]);
-  split_pair8(x0[2], x0[3], hs[1], ms[1], ls[1]);
-  split_pair8(x1[0], x1[1], hs[2], ms[2], ls[2]);
-  split_pair8(x1[2], x1[3], hs[3], ms[3], ls[3]);
-  Planes p;
-  p.h = __builtin_bit_cast(bf8, u32x4{hs[0], hs[1], hs[2], hs[3]});
-  p.m = __builtin_bit_cast(bf8, u32x4{ms[0], ms[1], ms[2], ms[3]});
-  p.l = __builtin_bit_cast(bf8, u32x4{ls[0], ls[1], ls[2], ls[3]});
-  return p;
-}
-
-__device__ __forceinline__ f32x16 mfma6x(const Planes& a, const Planes& b, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.m, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
-  return acc;
-}
-
-__device__ __forceinline__ void glds(const float* src, lds_char* dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const void*)src, (void __attribute__((address_space(3)))*)(
-                            (__attribute__((address_space(3))) char*)dst), 16, 0, 0);
-}
-
-__device__ __forceinline__ int swz8(int row) { return (row ^ (row >> 3)) & 7; }
 
 // NW = 8: waves 2 x 4, wave tile 128 x 64 (two waves per SIMD); NW = 4: waves 2 x 2, wave tile
 // 128 x 128 (one wave per SIMD, 256 accumulator registers: 0.67 split elements per MFMA)
@@ -128,10 +81,10 @@ gemm_emu8_kernel(E8Params p) {
     const int j = NPW * wid + i;
     const int row = j * 8 + (lane >> 3);
     const int gr = min(m0 + row, p.M - 1);
-    asrc[i] = p.A + (long)gr * p.lda + ((lane & 7) ^ swz8(row)) * 4;
+    asrc[i] = p.A + (long)gr * p.lda + ((lane & 7) ^ kswz(row)) * 4;
     if (BKC) {
       const int gc = min(n0 + row, p.N - 1);
-      bsrc[i] = p.B + (long)gc * p.ldb + ((lane & 7) ^ swz8(row)) * 4;
+      bsrc[i] = p.B + (long)gc * p.ldb + ((lane & 7) ^ kswz(row)) * 4;
     } else {
       const int gc = min(n0 + lane * 4, p.N - 4);
       bsrc[i] = p.B + (long)j * p.ldb + gc;  // k row j of the tile
@@ -141,10 +94,10 @@ gemm_emu8_kernel(E8Params p) {
   auto issue = [&](int kt) {
     lds_char* st = smem + (kt & 1) * kStage;
 #pragma unroll
-    for (int i = 0; i < NPW; ++i) glds(asrc[i] + (long)kt * kBK8, st + (NPW * wid + i) * 1024);
+    for (int i = 0; i < NPW; ++i) glds16(asrc[i] + (long)kt * kBK8, st + (NPW * wid + i) * 1024);
 #pragma unroll
     for (int i = 0; i < NPW; ++i)
-      glds(bsrc[i] + (long)kt * bstep, st + kImg + (NPW * wid + i) * 1024);
+      glds16(bsrc[i] + (long)kt * bstep, st + kImg + (NPW * wid + i) * 1024);
   };
 
   f32x16 acc[4][FN];
@@ -157,7 +110,7 @@ gemm_emu8_kernel(E8Params p) {
 
   issue(0);
   for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (kt + 1 < nk) issue(kt + 1);
     const lds_char* st = smem + (kt & 1) * kStage;
@@ -169,10 +122,10 @@ gemm_emu8_kernel(E8Params p) {
         for (int g = 0; g < FN; ++g) {
           const int row = wn * WNC + g * 32 + l31;
           const lds_char* rb = st + kImg + row * 128;
-          const f32x4 v0 = *reinterpret_cast<const f32x4*>(rb + (((4 * j + h) ^ swz8(row)) * 16));
+          const f32x4 v0 = *reinterpret_cast<const f32x4*>(rb + (((4 * j + h) ^ kswz(row)) * 16));
           const f32x4 v1 =
-              *reinterpret_cast<const f32x4*>(rb + (((4 * j + 2 + h) ^ swz8(row)) * 16));
-          bp[g] = split8(v0, v1);
+              *reinterpret_cast<const f32x4*>(rb + (((4 * j + 2 + h) ^ kswz(row)) * 16));
+          split3_x8(v0, v1, bp[g].h, bp[g].m, bp[g].l);
         }
       } else {
         // column tile g takes the interleaved columns 2 i + (g & 1) of the wave's 64-column
@@ -190,23 +143,26 @@ gemm_emu8_kernel(E8Params p) {
               x[0][u][s] = v[0];
               x[1][u][s] = v[1];
             }
-          bp[2 * pp] = split8(x[0][0], x[0][1]);
-          bp[2 * pp + 1] = split8(x[1][0], x[1][1]);
+#pragma unroll
+          for (int u = 0; u < 2; ++u)
+            split3_x8(x[u][0], x[u][1], bp[2 * pp + u].h, bp[2 * pp + u].m, bp[2 * pp + u].l);
         }
       }
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         const int row = wm * 128 + f * 32 + l31;
         const lds_char* ra = st + row * 128;
-        const f32x4 v0 = *reinterpret_cast<const f32x4*>(ra + (((4 * j + h) ^ swz8(row)) * 16));
-        const f32x4 v1 = *reinterpret_cast<const f32x4*>(ra + (((4 * j + 2 + h) ^ swz8(row)) * 16));
-        const Planes ap = split8(v0, v1);
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(ra + (((4 * j + h) ^ kswz(row)) * 16));
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(ra + (((4 * j + 2 + h) ^ kswz(row)) * 16));
+        Planes ap;
+        split3_x8(v0, v1, ap.h, ap.m, ap.l);
 #pragma unroll
-        for (int g = 0; g < FN; ++g) acc[f][g] = mfma6x(ap, bp[g], acc[f][g]);
+        for (int g = 0; g < FN; ++g)
+          acc[f][g] = mfma_emu6(ap.h, ap.m, ap.l, bp[g].h, bp[g].m, bp[g].l, acc[f][g]);
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may outlive the workgroup
+  wait_vmcnt<0>();  // no LDS-DMA may outlive the workgroup
 
   // epilogue: lane (h, l31) of tile (f, g) holds rows (r & 3) + 8 (r >> 2) + 4 h, column l31
   // (MN-contiguous B: column 2 l31 + (g & 1) of the 64-column group g >> 1)

@@ -37,6 +37,7 @@
 #include "conv.h"
 #include "kernels.h"
 #include "optim_elem.h"
+#include "split_bf16.h"
 
 namespace tdp {
 namespace {
@@ -91,65 +92,6 @@ struct FastParams {
   long ldg;
 };
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef char lds_char;  // generic pointer into the dynamic LDS array (reads infer ds_read)
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// ---- fp32 GEMM on the bf16 matrix core (EMU kernels) ----------------------------------------
-// gfx950 runs v_mfma_f32_32x32x2_f32 at 1/16 of the bf16 rate (64 vs 1024 FLOP/clk/SIMD). An
-// fp32 operand splits EXACTLY into three bf16 terms x = x0 + x1 + x2 (x0 = RNE_bf16(x),
-// x1 = RNE_bf16(x - x0), x2 = x - x0 - x1: 24 significand bits = 3 x 8, every subtraction exact),
-// so a*b = sum_ij a_i b_j with the six terms of weight >= 2^-16 kept and a1b2 + a2b1 + a2b2
-// (<= ~2^-24 |a||b|, the size of one fp32 rounding of the product) dropped. Each bf16 x bf16
-// product is exact in the fp32 accumulator, so the result carries fp32 accuracy (error bound
-// tested against fp64 next to the native f32 MFMA path: tests/test_gemm_emu_gpu.py) at 6 x 32
-// instead of 8 x 64 cycles per 32x32x16 step: a 2.67x higher matrix-core ceiling. The split
-// runs on the VALU from the SAME fp32 LDS fragments the f32 path reads (v_cvt_pk_bf16_f32 does
-// the RNE pair conversion), and overlaps the previous step's MFMAs.
-// K order: the bf16 MFMA gives lane half h the k-slots 8h..8h+7; the f32 fragment reads give
-// lane half h the k = 8q + 4h + s (s < 4) of two consecutive q -- the same permutation for A and
-// B, so the dot products are unchanged.
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m,
-                                            unsigned& l) {
-  // scalar f32 subtractions (built with -fno-slp-vectorize: no v_pk_add_f32)
-  const unsigned hu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf2));
-  const float r0 = x0 - __uint_as_float(hu << 16), r1 = x1 - __uint_as_float(hu & 0xffff0000u);
-  const unsigned mu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf2));
-  const float s0 = r0 - __uint_as_float(mu << 16), s1 = r1 - __uint_as_float(mu & 0xffff0000u);
-  h = hu;
-  m = mu;
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf2));
-}
-// 8 fp32 (two f32 k-steps of 4) -> three bf16x8 MFMA operands
-__device__ __forceinline__ void split3_x8(const float (&x0)[4], const float (&x1)[4], bf8& h,
-                                          bf8& m, bf8& l) {
-  unsigned hs[4], ms[4], ls[4];
-  split3_pair(x0[0], x0[1], hs[0], ms[0], ls[0]);
-  split3_pair(x0[2], x0[3], hs[1], ms[1], ls[1]);
-  split3_pair(x1[0], x1[1], hs[2], ms[2], ls[2]);
-  split3_pair(x1[2], x1[3], hs[3], ms[3], ls[3]);
-  const u32x4 hv = {hs[0], hs[1], hs[2], hs[3]};
-  const u32x4 mv = {ms[0], ms[1], ms[2], ms[3]};
-  const u32x4 lv = {ls[0], ls[1], ls[2], ls[3]};
-  h = __builtin_bit_cast(bf8, hv);
-  m = __builtin_bit_cast(bf8, mv);
-  l = __builtin_bit_cast(bf8, lv);
-}
-// acc += a*b over the six kept split terms (smallest first)
-__device__ __forceinline__ f32x16 mfma_emu6(const bf8& ah, const bf8& am, const bf8& al,
-                                            const bf8& bh, const bf8& bm, const bf8& bl,
-                                            f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-  return acc;
-}
-
 // optimizer-epilogue variant flags, or-ed into the OPTK template argument next to the kind
 constexpr int kOptWide = 4;  // wider HBM batches: register SGD both row tiles, LDS paths 2x loads
 constexpr int kOptNT = 8;    // non-temporal p / state loads and stores
@@ -171,24 +113,6 @@ __device__ __forceinline__ void st_epi(float* q, f32x2 v) {
   if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x2*>(q));
   else *reinterpret_cast<f32x2*>(q) = v;
 }
-
-__device__ __forceinline__ void glds16(const float* src, lds_char* dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const void*)src, (void __attribute__((address_space(3)))*)(
-          (__attribute__((address_space(3))) char*)dst), 16, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Row swizzle of K-contiguous tiles: slot(row, chunk) = chunk ^ swz(row). XOR-ing in row bits 3-5
-// makes every 16-lane group of a ds_read_b128 (rows r..r+31 of one fragment) hit 16 distinct
-// (row parity, slot) pairs = all 64 banks: conflict-free (plain `row & 7` left a 2-way conflict,
-// SQ_LDS_BANK_CONFLICT = 4 cycles per read in the first profile).
-__device__ __forceinline__ int swz(int row) { return (row ^ (row >> 3)) & 7; }
 
 // Per-lane source pointers of one operand's share of a K tile, computed once per workgroup:
 // only the k offset changes from tile to tile (clamped on the K tail).
@@ -213,7 +137,7 @@ struct TileSrc {
         int gr = r0 + row;
         gr = gr < rlim ? gr : rlim - 1;
         base[i] = g + (long)gr * ld;
-        koff[i] = ((lane & 7) ^ swz(row)) * 4;
+        koff[i] = ((lane & 7) ^ kswz(row)) * 4;
       } else {
         constexpr int LPR = R / 4;                 // lanes per 512-B row
         constexpr int RPC = 1024 / (R * 4);        // rows per chunk
@@ -280,7 +204,7 @@ struct ImSrcA {
         hb[i] = (int)y + cv.ph;
         wb[i] = (int)x + cv.pw;
       }
-      koff[i] = ((lane & 7) ^ swz(row)) * 4;
+      koff[i] = ((lane & 7) ^ kswz(row)) * 4;
     }
   }
 
@@ -530,7 +454,7 @@ __device__ __forceinline__ void gemm_tile(const FastParams& p, const int lid, ld
 #pragma unroll
       for (int f = 0; f < FM; ++f) {
         const int row = wm * WR + f * 32 + l31;
-        const int slot = (2 * q + h) ^ swz(row);
+        const int slot = (2 * q + h) ^ kswz(row);
         const f32x4 v = *reinterpret_cast<const f32x4*>(st + a_off[f] + slot * 16);
 #pragma unroll
         for (int s = 0; s < 4; ++s) a[f][s] = v[s];
@@ -548,7 +472,7 @@ __device__ __forceinline__ void gemm_tile(const FastParams& p, const int lid, ld
 #pragma unroll
       for (int g = 0; g < FN; ++g) {
         const int row = wn * (32 * FN) + g * 32 + l31;
-        const int slot = (2 * q + h) ^ swz(row);
+        const int slot = (2 * q + h) ^ kswz(row);
         const f32x4 v = *reinterpret_cast<const f32x4*>(st + b_off[g] + slot * 16);
 #pragma unroll
         for (int s = 0; s < 4; ++s) bb[g][s] = v[s];
@@ -1433,7 +1357,7 @@ void launch_fast(const FastParams& p, int nblocks, hipStream_t s) {
                      dim3(kT), lds, s, p);
 }
 
-// fp32 products on the bf16 matrix core (split3 emulation, see split3_pair) unless
+// fp32 products on the bf16 matrix core (split3 emulation, see split_bf16.h) unless
 // TDP_GEMM_EMU=0 (or gemm_f32_set_emu(false)) selects the native v_mfma_f32_32x32x2_f32 path
 // same-box A/B (profiles/micro/gemm_emu_prio_ab_r4l.txt): toy MLP 0.4069 -> 0.3975 ms/step,
 // ResNet-50 35.57 -> 35.43; the isolated GEMMs do not move.

@@ -6,8 +6,8 @@
 // K = 4096-9216) the small operand A is re-read by every column tile -- 32 tiles x 2 column waves
 // = 64 redundant splits of each activation -- while the weight B is streamed from HBM once. Here
 // A is split ONCE (by its producer: the gather / split-K reduce / loss head, or split_planes) into
-// exact bf16 hi / mid / lo planes x = x0 + x1 + x2 (csrc/gemm_f32_fast.hip split3_pair: the same
-// RNE conversions, so the planes are bit-identical to the in-kernel split), and the kernel is
+// exact bf16 hi / mid / lo planes x = x0 + x1 + x2 (split_bf16.h split3_bits: the definition the
+// in-kernel split uses, so the planes are bit-identical to it), and the kernel is
 // laid out so that each weight fragment is split by exactly ONE wave:
 //   * block tile 128 (all batch rows) x 128 columns, 4 waves side by side (1 x 4): wave w owns
 //     columns 32w..32w+31 and all four 32-row MFMA tiles, so its one B fragment per 16-deep K step
@@ -36,6 +36,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "planes.h"
+#include "split_bf16.h"
 
 namespace tdp {
 namespace {
@@ -45,13 +46,6 @@ constexpr int kBK = 32;
 constexpr int kBM = 128, kBN = 128;
 constexpr int kAPlane = kBM * kBK * 2;  // 8 KiB: [128 rows][32 k] bf16
 constexpr int kABytes = 3 * kAPlane;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef char lds_char;
 
 struct PParams {
   const uint16_t* Ap;
@@ -71,48 +65,7 @@ struct PParams {
   int prio;
 };
 
-// exact 3-way bf16 split of a pair (identical instruction sequence to gemm_f32_fast.hip
-// split3_pair: RNE v_cvt_pk_bf16_f32, scalar f32 residuals)
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned& h, unsigned& m,
-                                           unsigned& l) {
-  const unsigned hu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf2));
-  const float r0 = x0 - __uint_as_float(hu << 16), r1 = x1 - __uint_as_float(hu & 0xffff0000u);
-  const unsigned mu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf2));
-  const float s0 = r0 - __uint_as_float(mu << 16), s1 = r1 - __uint_as_float(mu & 0xffff0000u);
-  h = hu;
-  m = mu;
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf2));
-}
-
-__device__ __forceinline__ void split_x8(const float (&x)[8], bf8& h, bf8& m, bf8& l) {
-  unsigned hs[4], ms[4], ls[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) split_pair(x[2 * i], x[2 * i + 1], hs[i], ms[i], ls[i]);
-  h = __builtin_bit_cast(bf8, u32x4{hs[0], hs[1], hs[2], hs[3]});
-  m = __builtin_bit_cast(bf8, u32x4{ms[0], ms[1], ms[2], ms[3]});
-  l = __builtin_bit_cast(bf8, u32x4{ls[0], ls[1], ls[2], ls[3]});
-}
-
-// acc += a*b over the six kept split terms (smallest first; a1b2 + a2b1 + a2b2 dropped)
-__device__ __forceinline__ f32x16 mfma6(const bf8& ah, const bf8& am, const bf8& al, const bf8& bh,
-                                        const bf8& bm, const bf8& bl, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-  return acc;
-}
-
-__device__ __forceinline__ void glds16(const void* src, lds_char* dst) {
-  __builtin_amdgcn_global_load_lds(
-      src, (void __attribute__((address_space(3)))*)(
-               (__attribute__((address_space(3))) char*)dst), 16, 0, 0);
-}
-
 __device__ __forceinline__ int aswz(int row) { return (row >> 2) & 3; }
-__device__ __forceinline__ int bswz(int row) { return (row ^ (row >> 3)) & 7; }
 
 // bias, ReLU, gate of four adjacent finished outputs, then C (16-B store) and, when requested,
 // the three bf16 planes of the result (8-B stores); returns the stored value
@@ -129,21 +82,17 @@ __device__ __forceinline__ f32x4 finish4(const PParams& p, int row, int col, f32
   }
   *reinterpret_cast<f32x4*>(p.C + (long)row * p.ldc + col) = v;
   if (p.op) {
+    // store_planes4, open-coded: the address formed after the splits (the compiler schedules
+    // the epilogue differently when it is formed before them, as an argument would be)
     unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(v[0], v[1], h0, m0, l0);
-    split_pair(v[2], v[3], h1, m1, l1);
+    split3_bits(v[0], v[1], h0, m0, l0);
+    split3_bits(v[2], v[3], h1, m1, l1);
     uint16_t* o = p.op + (long)row * p.N + col;
     *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
     *reinterpret_cast<u32x2*>(o + p.ops) = u32x2{m0, m1};
     *reinterpret_cast<u32x2*>(o + 2 * p.ops) = u32x2{l0, l1};
   }
   return v;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // S pipeline stages; WN 32-column MFMA tiles per wave (block tile 128 x 128*WN: WN = 2 halves
@@ -195,7 +144,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
     if (BKC) {  // [BN rows][32 k] fp32, 128-B rows, 8 rows per chunk
       const int row = j * 8 + (lane >> 3);
       const int gr = min(n0 + row, p.N - 1);
-      bbase[i] = p.B + (long)gr * p.ldb + ((lane & 7) ^ bswz(row)) * 4;
+      bbase[i] = p.B + (long)gr * p.ldb + ((lane & 7) ^ kswz(row)) * 4;
     } else {    // [32 k][BN cols] fp32, BN*4-B rows, 1024 / (BN*4) rows per chunk
       constexpr int LPR = BN / 4, RPC = 1024 / (BN * 4);
       const int krow = RPC * j + lane / LPR;
@@ -248,9 +197,9 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
     if (BKC) {
       const int c0 = 4 * s + 2 * h;
       const f32x4 v0 =
-          *reinterpret_cast<const f32x4*>(st + kABytes + bcol * 128 + ((c0 ^ bswz(bcol)) * 16));
+          *reinterpret_cast<const f32x4*>(st + kABytes + bcol * 128 + ((c0 ^ kswz(bcol)) * 16));
       const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + kABytes + bcol * 128 +
-                                                       (((c0 + 1) ^ bswz(bcol)) * 16));
+                                                       (((c0 + 1) ^ kswz(bcol)) * 16));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         bv[j] = v0[j];
@@ -292,7 +241,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
                                                  ((h ^ aswz(row)) * 16));
       }
     __builtin_amdgcn_sched_barrier(0);
-    split_x8(b0, x0[0], x0[1], x0[2]);
+    split3_x8(b0, x0[0], x0[1], x0[2]);
 #pragma unroll
     for (int f = 2; f < 4; ++f)
 #pragma unroll
@@ -306,21 +255,22 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
     // B split (in-order LDS returns keep every wait a counted lgkmcnt <= 9)
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      acc[f][0] = mfma6(a0[f][0], a0[f][1], a0[f][2], x0[0], x0[1], x0[2], acc[f][0]);
+      acc[f][0] = mfma_emu6(a0[f][0], a0[f][1], a0[f][2], x0[0], x0[1], x0[2], acc[f][0]);
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         const int row = f * 32 + l31;
         a1[f][q] = *reinterpret_cast<const bf8*>(st + q * kAPlane + row * 64 +
                                                  (((2 + h) ^ aswz(row)) * 16));
       }
-      split_pair(b1[2 * f], b1[2 * f + 1], h1[f], m1[f], l1[f]);
+      split3_bits(b1[2 * f], b1[2 * f + 1], h1[f], m1[f], l1[f]);
       __builtin_amdgcn_sched_barrier(0);
     }
     const bf8 y0 = __builtin_bit_cast(bf8, u32x4{h1[0], h1[1], h1[2], h1[3]});
     const bf8 y1 = __builtin_bit_cast(bf8, u32x4{m1[0], m1[1], m1[2], m1[3]});
     const bf8 y2 = __builtin_bit_cast(bf8, u32x4{l1[0], l1[1], l1[2], l1[3]});
 #pragma unroll
-    for (int f = 0; f < 4; ++f) acc[f][0] = mfma6(a1[f][0], a1[f][1], a1[f][2], y0, y1, y2, acc[f][0]);
+    for (int f = 0; f < 4; ++f)
+      acc[f][0] = mfma_emu6(a1[f][0], a1[f][1], a1[f][2], y0, y1, y2, acc[f][0]);
   };
   if constexpr (S == 3) {
     // Cross-tile pipeline (three stages, one workgroup = one wave per SIMD): a tile's B fragments
@@ -347,7 +297,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
       read_a(smem, 0, 0, a0);
       read_a(smem, 0, 1, a0);
       __builtin_amdgcn_sched_barrier(0);
-      split_x8(b0, x0[0], x0[1], x0[2]);
+      split3_x8(b0, x0[0], x0[1], x0[2]);
       read_a(smem, 0, 2, a0);
       read_a(smem, 0, 3, a0);
     }
@@ -376,9 +326,9 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
       // step 0 of tile kt (24 MFMAs); step-1 A reads (12) and the step-1 B split (~36 VALU)
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
-        acc[f][0] = mfma6(a0[f][0], a0[f][1], a0[f][2], x0[0], x0[1], x0[2], acc[f][0]);
+        acc[f][0] = mfma_emu6(a0[f][0], a0[f][1], a0[f][2], x0[0], x0[1], x0[2], acc[f][0]);
         read_a(st, 1, f, a1);
-        split_pair(b1[2 * f], b1[2 * f + 1], h1[f], m1[f], l1[f]);
+        split3_bits(b1[2 * f], b1[2 * f + 1], h1[f], m1[f], l1[f]);
       }
 #pragma unroll
       for (int u = 0; u < 12; ++u) {
@@ -404,7 +354,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
       // (12), then its step-0 B split (~36 VALU) once the B reads have returned
       read_b(sn, 0, b0);
       read_b(sn, 1, b1);
-      acc[0][0] = mfma6(a1[0][0], a1[0][1], a1[0][2], y0, y1, y2, acc[0][0]);
+      acc[0][0] = mfma_emu6(a1[0][0], a1[0][1], a1[0][2], y0, y1, y2, acc[0][0]);
       read_a(sn, 0, 0, a0);
       __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
@@ -418,10 +368,10 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 :
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int f = 1; f < 4; ++f) {
-        acc[f][0] = mfma6(a1[f][0], a1[f][1], a1[f][2], y0, y1, y2, acc[f][0]);
+        acc[f][0] = mfma_emu6(a1[f][0], a1[f][1], a1[f][2], y0, y1, y2, acc[f][0]);
         read_a(sn, 0, f, a0);
       }
-      split_x8(b0, x0[0], x0[1], x0[2]);
+      split3_x8(b0, x0[0], x0[1], x0[2]);
 #pragma unroll
       for (int u = 0; u < 9; ++u) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -557,7 +507,7 @@ gemm_planes_dual_kernel(PParams p) {
         const int row = jb * 8 + (lane >> 3);
         const int gr = min(n0 + row, p.N - 1);
         src[i] = reinterpret_cast<const char*>(p.B + (long)gr * p.ldb +
-                                               ((lane & 7) ^ bswz(row)) * 4);
+                                               ((lane & 7) ^ kswz(row)) * 4);
         kbytes[i] = 4;
       } else {
         constexpr int LPR = BN / 4, RPC = 1024 / (BN * 4);
@@ -589,9 +539,9 @@ gemm_planes_dual_kernel(PParams p) {
     if (BKC) {
       const int c0 = 4 * q + 2 * h;
       const f32x4 v0 =
-          *reinterpret_cast<const f32x4*>(st + kABytes + bcol * 128 + ((c0 ^ bswz(bcol)) * 16));
+          *reinterpret_cast<const f32x4*>(st + kABytes + bcol * 128 + ((c0 ^ kswz(bcol)) * 16));
       const f32x4 v1 = *reinterpret_cast<const f32x4*>(st + kABytes + bcol * 128 +
-                                                       (((c0 + 1) ^ bswz(bcol)) * 16));
+                                                       (((c0 + 1) ^ kswz(bcol)) * 16));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         bv[j] = v0[j];
@@ -613,9 +563,9 @@ gemm_planes_dual_kernel(PParams p) {
         a[f][pl] = *reinterpret_cast<const bf8*>(st + pl * kAPlane + off);
     }
     bf8 x0, x1, x2;
-    split_x8(bv, x0, x1, x2);
+    split3_x8(bv, x0, x1, x2);
 #pragma unroll
-    for (int f = 0; f < 4; ++f) acc[f] = mfma6(a[f][0], a[f][1], a[f][2], x0, x1, x2, acc[f]);
+    for (int f = 0; f < 4; ++f) acc[f] = mfma_emu6(a[f][0], a[f][1], a[f][2], x0, x1, x2, acc[f]);
   };
 
   if (nk > 0) {
@@ -693,13 +643,7 @@ __global__ __launch_bounds__(kT) void split_planes_kernel(const float* __restric
     const long e0 = idx * 4;
     const int row = (int)(e0 / cols), col = (int)(e0 - (long)row * cols);
     const f32x4 v = *reinterpret_cast<const f32x4*>(x + (long)row * ldx + col);
-    unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(v[0], v[1], h0, m0, l0);
-    split_pair(v[2], v[3], h1, m1, l1);
-    uint16_t* o = planes + (long)row * cols + col;
-    *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
-    *reinterpret_cast<u32x2*>(o + ps) = u32x2{m0, m1};
-    *reinterpret_cast<u32x2*>(o + 2 * ps) = u32x2{l0, l1};
+    store_planes4(planes + (long)row * cols + col, ps, v[0], v[1], v[2], v[3]);
   }
 }
 
@@ -729,12 +673,7 @@ __global__ __launch_bounds__(kT) void gather_planes_kernel(const float* __restri
   for (long k = threadIdx.x + (long)kT * blockIdx.y; k < F4; k += step) {
     const f32x4 v = src[k];
     dst[k] = v;
-    unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(v[0], v[1], h0, m0, l0);
-    split_pair(v[2], v[3], h1, m1, l1);
-    *reinterpret_cast<u32x2*>(o + 4 * k) = u32x2{h0, h1};
-    *reinterpret_cast<u32x2*>(o + ps + 4 * k) = u32x2{m0, m1};
-    *reinterpret_cast<u32x2*>(o + 2 * ps + 4 * k) = u32x2{l0, l1};
+    store_planes4(o + 4 * k, ps, v[0], v[1], v[2], v[3]);
   }
   if (threadIdx.x == 0 && blockIdx.y == 0) yb[b] = y[i];
   if (cursor) {

@@ -21,6 +21,7 @@
 #include "kernels.h"
 #include "optim_elem.h"
 #include "planes.h"
+#include "split_bf16.h"
 
 namespace tdp {
 namespace {
@@ -208,19 +209,6 @@ __device__ __forceinline__ void opt_apply(const OptEpilogue& o, long i, float g)
   }
 }
 
-__device__ __forceinline__ void split4_pair(float x0, float x1, unsigned& h, unsigned& m,
-                                            unsigned& l) {
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf2_ __attribute__((ext_vector_type(2)));
-  const unsigned hu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_{x0, x1}, bf2_));
-  const float r0 = x0 - __uint_as_float(hu << 16), r1 = x1 - __uint_as_float(hu & 0xffff0000u);
-  const unsigned mu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_{r0, r1}, bf2_));
-  const float s0 = r0 - __uint_as_float(mu << 16), s1 = r1 - __uint_as_float(mu & 0xffff0000u);
-  h = hu;
-  m = mu;
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_{s0, s1}, bf2_));
-}
-
 // weight-gradient columns per head_bwd workgroup: 32 when separate workgroups compute dx; 16
 // with the in-place update, where each weight workgroup also computes dx for its own columns
 // (twice the workgroups for the same work)
@@ -251,15 +239,14 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdParams p) {
       for (int e = 0; e < 4; ++e) acc[e] = gv[e] > 0.f ? acc[e] : 0.f;
     }
     *reinterpret_cast<f32x4*>(p.dx + (long)row * p.lddx + col) = acc;
-    if (p.dxp) {
-      typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
+    if (p.dxp) {  // store_planes4, open-coded (as gemm_planes.hip finish4)
       unsigned h0, m0, l0, h1, m1, l1;
-      split4_pair(acc[0], acc[1], h0, m0, l0);
-      split4_pair(acc[2], acc[3], h1, m1, l1);
+      split3_bits(acc[0], acc[1], h0, m0, l0);
+      split3_bits(acc[2], acc[3], h1, m1, l1);
       uint16_t* o = p.dxp + (long)row * p.I + col;
-      *reinterpret_cast<u32x2_*>(o) = u32x2_{h0, h1};
-      *reinterpret_cast<u32x2_*>(o + p.dxps) = u32x2_{m0, m1};
-      *reinterpret_cast<u32x2_*>(o + 2 * p.dxps) = u32x2_{l0, l1};
+      *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
+      *reinterpret_cast<u32x2*>(o + p.dxps) = u32x2{m0, m1};
+      *reinterpret_cast<u32x2*>(o + 2 * p.dxps) = u32x2{l0, l1};
     }
     return;
   }
@@ -321,15 +308,14 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdParams p) {
           for (int e = 0; e < 4; ++e) a4[e] = gt[e] > 0.f ? a4[e] : 0.f;
         }
         *reinterpret_cast<f32x4*>(p.dx + (long)row * p.lddx + c0) = a4;
-        if (p.dxp) {
-          typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
+        if (p.dxp) {  // store_planes4, open-coded (as gemm_planes.hip finish4)
           unsigned h0, m0, l0, h1, m1, l1;
-          split4_pair(a4[0], a4[1], h0, m0, l0);
-          split4_pair(a4[2], a4[3], h1, m1, l1);
+          split3_bits(a4[0], a4[1], h0, m0, l0);
+          split3_bits(a4[2], a4[3], h1, m1, l1);
           uint16_t* o = p.dxp + (long)row * p.I + c0;
-          *reinterpret_cast<u32x2_*>(o) = u32x2_{h0, h1};
-          *reinterpret_cast<u32x2_*>(o + p.dxps) = u32x2_{m0, m1};
-          *reinterpret_cast<u32x2_*>(o + 2 * p.dxps) = u32x2_{l0, l1};
+          *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
+          *reinterpret_cast<u32x2*>(o + p.dxps) = u32x2{m0, m1};
+          *reinterpret_cast<u32x2*>(o + 2 * p.dxps) = u32x2{l0, l1};
         }
       }
     }
@@ -520,15 +506,14 @@ __global__ __launch_bounds__(256) void head_ce_kernel(HeadCeParams p) {
         for (int e = 0; e < 4; ++e) s4[e] = gv[e] > 0.f ? s4[e] : 0.f;
       }
       *reinterpret_cast<f32x4*>(p.dx + (long)row * p.lddx + col) = s4;
-      if (p.dxp) {
-        typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
+      if (p.dxp) {  // store_planes4, open-coded (as gemm_planes.hip finish4)
         unsigned h0, m0, l0, h1, m1, l1;
-        split4_pair(s4[0], s4[1], h0, m0, l0);
-        split4_pair(s4[2], s4[3], h1, m1, l1);
+        split3_bits(s4[0], s4[1], h0, m0, l0);
+        split3_bits(s4[2], s4[3], h1, m1, l1);
         uint16_t* o = p.dxp + (long)row * p.I + col;
-        *reinterpret_cast<u32x2_*>(o) = u32x2_{h0, h1};
-        *reinterpret_cast<u32x2_*>(o + p.dxps) = u32x2_{m0, m1};
-        *reinterpret_cast<u32x2_*>(o + 2 * p.dxps) = u32x2_{l0, l1};
+        *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
+        *reinterpret_cast<u32x2*>(o + p.dxps) = u32x2{m0, m1};
+        *reinterpret_cast<u32x2*>(o + 2 * p.dxps) = u32x2{l0, l1};
       }
     }
   }
