@@ -1102,12 +1102,23 @@ ConvGeom nhwc_geom(const std::vector<int64_t>& xs, int64_t cout, int64_t R, int6
 
 Tensor conv_nhwc_exec(int mode, const ConvGeom& g, const Tensor& A, const Tensor& B, Tensor C,
                       const c10::optional<Tensor>& bias, bool relu, double beta,
-                      const WeightTaps* wtap = nullptr, Tensor* stats = nullptr) {
+                      const WeightTaps* wtap = nullptr, Tensor* stats = nullptr,
+                      bool bf16 = false) {
   TORCH_CHECK(conv_nhwc_ok(mode, g), "conv (NHWC): channels must be multiples of 4 and "
               "input-gradient strides powers of two");
-  const ConvPlan pl = conv_nhwc_plan(mode, g, num_cus(C.get_device()));
+  const int cus = num_cus(C.get_device());
+  const ConvPlan pl = bf16 ? conv_bf16_plan(mode, g, cus) : conv_nhwc_plan(mode, g, cus);
   Tensor ws;
   if (pl.ws_floats > 0) ws = at::empty({pl.ws_floats}, C.options());
+  if (bf16) {
+    // mixed precision (conv_bf16.hip): operands rounded once to bf16; no statistics epilogue
+    TORCH_CHECK(stats == nullptr, "conv (NHWC, bf16): no statistics epilogue");
+    TORCH_CHECK(beta == 0.0 || beta == 1.0, "conv (NHWC, bf16): beta must be 0 or 1");
+    conv_bf16_run(pl, g, A.data_ptr<float>(), B.data_ptr<float>(), C.data_ptr<float>(),
+                  fptr(bias), relu, (float)beta,
+                  pl.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream(), wtap);
+    return C;
+  }
   Tensor st;
   if (stats != nullptr && pl.splits == 1)
     st = at::empty({(pl.M + pl.bm - 1) / pl.bm, 3, (int64_t)pl.N}, C.options());
@@ -1130,7 +1141,7 @@ void check_weight_cl(const Tensor& w) {
 // written there as out = dgrad + beta * out (a residual block's shared input gradient)
 Tensor conv_nhwc_dgrad_w_op(const Tensor& dy, const Tensor& w, std::vector<int64_t> x_shape,
                             int64_t sh, int64_t sw, int64_t ph, int64_t pw,
-                            const c10::optional<Tensor>& out, double beta) {
+                            const c10::optional<Tensor>& out, double beta, bool bf16) {
   CHECK_GPU(dy); CHECK_F32(dy); CHECK_CL(dy);
   check_weight_cl(w);
   const int64_t R = w.size(2), S = w.size(3);
@@ -1148,13 +1159,13 @@ Tensor conv_nhwc_dgrad_w_op(const Tensor& dy, const Tensor& w, std::vector<int64
     dx = at::empty(x_shape, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
   }
   const WeightTaps t{(int)R, (int)S, 0, 0, 1, 1};
-  return conv_nhwc_exec(kConvDgrad, g, dy, w, dx, c10::nullopt, false, beta, &t);
+  return conv_nhwc_exec(kConvDgrad, g, dy, w, dx, c10::nullopt, false, beta, &t, nullptr, bf16);
 }
 
 // One stride phase of a strided input gradient with the phase's taps read from the weight
 Tensor conv_nhwc_dgrad_phase_w_op(const Tensor& dy, const Tensor& w, int64_t Hp, int64_t Wp,
                                   int64_t Rp, int64_t Sp, int64_t da, int64_t db, int64_t r0,
-                                  int64_t s0, int64_t sh, int64_t sw) {
+                                  int64_t s0, int64_t sh, int64_t sw, bool bf16) {
   CHECK_GPU(dy); CHECK_F32(dy); CHECK_CL(dy);
   check_weight_cl(w);
   ConvGeom g;
@@ -1169,7 +1180,7 @@ Tensor conv_nhwc_dgrad_phase_w_op(const Tensor& dy, const Tensor& w, int64_t Hp,
   auto out = at::empty({g.N, (int64_t)g.C, Hp, Wp},
                        dy.options().memory_format(at::MemoryFormat::ChannelsLast));
   const WeightTaps t{(int)w.size(2), (int)w.size(3), (int)r0, (int)s0, (int)sh, (int)sw};
-  return conv_nhwc_exec(kConvDgrad, g, dy, w, out, c10::nullopt, false, 0.0, &t);
+  return conv_nhwc_exec(kConvDgrad, g, dy, w, out, c10::nullopt, false, 0.0, &t, nullptr, bf16);
 }
 
 // dst = src over dst's logical shape (any strides); where an index is outside src's shape the
@@ -1190,13 +1201,13 @@ void copy4d_op(Tensor& dst, const Tensor& src, bool accumulate) {
 // x channels_last [N,C,H,W]; wt [Cout, R*S*C] (k = (r, s, c)) -> y channels_last
 Tensor conv_nhwc_fwd_op(const Tensor& x, const Tensor& wt, const c10::optional<Tensor>& bias,
                         int64_t R, int64_t S, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
-                        bool relu) {
+                        bool relu, bool bf16) {
   CHECK_GPU(x); CHECK_F32(x); CHECK_CL(x); CHECK_GPU(wt); CHECK_CONTIG(wt);
   const ConvGeom g = nhwc_geom(x.sizes().vec(), wt.size(0), R, S, sh, sw, ph, pw);
   TORCH_CHECK(wt.numel() == (int64_t)g.Cout * R * S * g.C, "conv (NHWC): weight size mismatch");
   if (bias.has_value() && bias->defined()) TORCH_CHECK(bias->numel() == g.Cout, "bias size");
   auto y = at::empty({g.N, g.Cout, g.P, g.Q}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  return conv_nhwc_exec(kConvFwd, g, x, wt, y, bias, relu, 0.0);
+  return conv_nhwc_exec(kConvFwd, g, x, wt, y, bias, relu, 0.0, nullptr, nullptr, bf16);
 }
 
 // Forward that also returns the output's per-tile column (count, mean, M2) for a following
@@ -1257,12 +1268,23 @@ Tensor conv_nhwc_dgrad_phase_op(const Tensor& dy, const Tensor& w2p, int64_t C, 
 
 // dy channels_last, x channels_last -> dwt [Cout, R*S*C] (dwt = beta*dwt + grad)
 void conv_nhwc_wgrad_op(const Tensor& dy, const Tensor& x, Tensor& dwt, int64_t R, int64_t S,
-                        int64_t sh, int64_t sw, int64_t ph, int64_t pw, double beta) {
+                        int64_t sh, int64_t sw, int64_t ph, int64_t pw, double beta, bool bf16) {
   CHECK_GPU(dy); CHECK_F32(dy); CHECK_CL(dy); CHECK_CL(x); CHECK_CONTIG(dwt);
   const ConvGeom g = nhwc_geom(x.sizes().vec(), dy.size(1), R, S, sh, sw, ph, pw);
   TORCH_CHECK(dy.size(2) == g.P && dy.size(3) == g.Q, "wgrad: dy shape");
   TORCH_CHECK(dwt.numel() == (int64_t)g.Cout * R * S * g.C, "wgrad: dw size mismatch");
-  conv_nhwc_exec(kConvWgrad, g, dy, x, dwt, c10::nullopt, false, beta);
+  conv_nhwc_exec(kConvWgrad, g, dy, x, dwt, c10::nullopt, false, beta, nullptr, nullptr, bf16);
+}
+
+// {splits, k_per_split} of the bf16 convolution's plan for a pass (0 forward, 1 input gradient,
+// 2 weight gradient) of this geometry
+std::vector<int64_t> conv_bf16_plan_op(int64_t mode, std::vector<int64_t> x_shape, int64_t cout,
+                                       int64_t R, int64_t S, int64_t sh, int64_t sw, int64_t ph,
+                                       int64_t pw) {
+  TORCH_CHECK(mode >= kConvFwd && mode <= kConvWgrad, "conv_bf16_plan: mode 0, 1 or 2");
+  const ConvGeom g = nhwc_geom(x_shape, cout, R, S, sh, sw, ph, pw);
+  const ConvPlan pl = conv_bf16_plan((int)mode, g, num_cus((int)c10::hip::current_device()));
+  return {pl.splits, pl.k_per_split};
 }
 
 // NHWC pooling: x channels_last -> y channels_last
@@ -1954,16 +1976,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scale_", &scale_op);
   m.def("cast_f32_bf16", &cast_f32_bf16_op);
   m.def("conv2d_fwd", &conv2d_fwd_op);
-  m.def("conv_nhwc_fwd", &conv_nhwc_fwd_op);
+  // bf16 = true: the same op in bf16 mixed precision (conv_bf16.hip), fp32 tensors
+  m.def("conv_nhwc_fwd", &conv_nhwc_fwd_op, py::arg("x"), py::arg("wt"), py::arg("bias"),
+        py::arg("R"), py::arg("S"), py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"),
+        py::arg("relu"), py::arg("bf16") = false);
   m.def("conv_nhwc_dgrad", &conv_nhwc_dgrad_op);
-  m.def("conv_nhwc_wgrad", &conv_nhwc_wgrad_op);
+  m.def("conv_nhwc_wgrad", &conv_nhwc_wgrad_op, py::arg("dy"), py::arg("x"), py::arg("dwt"),
+        py::arg("R"), py::arg("S"), py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"),
+        py::arg("beta"), py::arg("bf16") = false);
   m.def("conv_nhwc_dgrad_phase", &conv_nhwc_dgrad_phase_op);
   m.def("conv_nhwc_fwd_stats", &conv_nhwc_fwd_stats_op);
   m.def("bn_moments_partials", &bn_moments_partials_op, py::arg("part"), py::arg("count"));
   m.def("conv_nhwc_dgrad_w", &conv_nhwc_dgrad_w_op, py::arg("dy"), py::arg("w"),
         py::arg("x_shape"), py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"),
-        py::arg("out") = py::none(), py::arg("beta") = 0.0);
-  m.def("conv_nhwc_dgrad_phase_w", &conv_nhwc_dgrad_phase_w_op);
+        py::arg("out") = py::none(), py::arg("beta") = 0.0, py::arg("bf16") = false);
+  m.def("conv_nhwc_dgrad_phase_w", &conv_nhwc_dgrad_phase_w_op, py::arg("dy"), py::arg("w"),
+        py::arg("Hp"), py::arg("Wp"), py::arg("Rp"), py::arg("Sp"), py::arg("da"), py::arg("db"),
+        py::arg("r0"), py::arg("s0"), py::arg("sh"), py::arg("sw"), py::arg("bf16") = false);
+  m.def("conv_bf16_plan", &conv_bf16_plan_op, py::arg("mode"), py::arg("x_shape"),
+        py::arg("cout"), py::arg("R"), py::arg("S"), py::arg("sh"), py::arg("sw"), py::arg("ph"),
+        py::arg("pw"));
   m.def("copy4d", &copy4d_op, py::arg("dst"), py::arg("src"), py::arg("accumulate") = false);
   m.def("conv_wgrad_transposed", [](int64_t cout, int64_t R, int64_t S, int64_t C) {
     ConvGeom g{};

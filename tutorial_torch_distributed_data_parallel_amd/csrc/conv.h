@@ -50,6 +50,16 @@ bool conv_nhwc_run(const ConvPlan& pl, const ConvGeom& g, const float* A, const 
                    float* C, const float* bias, bool relu, float beta, float* ws,
                    hipStream_t s, const WeightTaps* wtap = nullptr, float* stats = nullptr);
 
+// The same convolutions in bf16 mixed precision (conv_bf16.hip): fp32 tensors, every operand
+// element rounded once to bf16, fp32 accumulation. Requires C % 4 == 0 and Cout % 4 == 0; the
+// input gradient takes stride-1 geometry with weight taps only (A = dy, B = the weight's
+// [Cout][Rf][Sf][C] memory); the weight gradient is always C = dWt [Cout][R*S*C]. The plan uses
+// gemm_bf16's split rule and never the measured fp32 plan table; beta in {0, 1}.
+ConvPlan conv_bf16_plan(int mode, const ConvGeom& g, int num_cus);
+void conv_bf16_run(const ConvPlan& pl, const ConvGeom& g, const float* A, const float* B,
+                   float* C, const float* bias, bool relu, float beta, float* ws, hipStream_t s,
+                   const WeightTaps* wtap = nullptr);
+
 // NCHW ReLU backward + per-channel bias gradient: g = dy*(y>0) (if y), db = sum over n,hw.
 int chan_splits(int N, int C, int HW, int num_cus);
 void chan_relu_bias_bwd(const float* dy, const float* y, int N, int C, int HW, float* g,

@@ -7,7 +7,8 @@
 // of its VALU split. The products of two bf16 values are exact in fp32, so the only error beyond
 // the operand rounding is the fp32 accumulation.
 //
-// Layout of the kernel:
+// Layout of the kernel (the tile itself -- loaders, LDS image, MFMA loop, epilogue -- is
+// bf16_tile.h, shared with the convolutions of conv_bf16.hip):
 //   * block tile 128 x 128, 64-deep K tile, 256 threads = 2 x 2 waves of 64 x 64 (2 x 2 MFMA
 //     tiles, 16 MFMAs per wave per K tile);
 //   * global_load_lds copies raw bytes and cannot convert, so operands are staged through
@@ -33,204 +34,21 @@
 
 #include "common.h"
 #include "kernels.h"
-#include "split_bf16.h"  // the vector typedefs
+#include "bf16_tile.h"  // the tile: loaders, LDS image, MFMA loop, epilogue
 
 namespace tdp {
+using namespace bf16t;
 namespace {
-
-constexpr int kT = 256;
-constexpr int kBM = 128, kBN = 128, kBK = 64;
-constexpr int kRowB = kBK * 2;          // LDS row: 64 bf16
-constexpr int kOpB = kBM * kRowB;       // 16 KiB per operand tile
-constexpr int kStageB = 2 * kOpB;       // A + B
-constexpr int kLdsB = 2 * kStageB;      // two stages
-
-struct BParams {
-  const float* A;
-  const float* B;
-  float* C;
-  float* ws;
-  const float* bias;
-  const float* gate;
-  long lda, ldb, ldc, ldg;
-  int M, N, K, kps, splits, tiles_n, tiles_mn;
-  int relu, beta;
-};
-
-// two fp32 -> packed bf16, round-to-nearest-even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack2(float x0, float x1) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf2));
-}
-
-__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-
-// One operand tile ([128 rows][64 k]) global -> registers. P: the operand, R rows (M or N), r0
-// the tile's first row, k0 the tile's first k, ke the end of this split's K range.
-//   KC (K-contiguous, [R][K]): unit u = i * 256 + t is chunk u & 7 of row u >> 3 (four units)
-//   else (MN-contiguous, [K][R]): thread t holds k-group t & 7 (8 k) of rows 4 (t >> 3) .. + 3
-template <bool KC, bool GUARD>
-__device__ __forceinline__ void load_tile(const float* __restrict__ P, long ld, int R, int r0,
-                                          int k0, int ke, float (&v)[32]) {
-  const int t = threadIdx.x;
-  if (KC) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int u = i * kT + t, row = u >> 3, c = u & 7;
-      if (GUARD) {
-        const int gr = r0 + row;
-        const float* src = P + (long)gr * ld;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int k = k0 + c * 8 + e;
-          v[8 * i + e] = (gr < R && k < ke) ? src[k] : 0.f;
-        }
-      } else {
-        // rows past the end are clamped: their outputs are discarded
-        const float* src = P + (long)min(r0 + row, R - 1) * ld + k0 + c * 8;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(src);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(src + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[8 * i + e] = a[e];
-          v[8 * i + 4 + e] = b[e];
-        }
-      }
-    }
-  } else {
-    const int kg = t & 7, col = (t >> 3) * 4;
-    if (GUARD) {
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        const int k = k0 + kg * 8 + kk;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int gr = r0 + col + j;
-          v[4 * kk + j] = (k < ke && gr < R) ? P[(long)k * ld + gr] : 0.f;
-        }
-      }
-    } else {
-      // R % 4 == 0: a quad of rows is wholly inside or wholly outside (clamped, discarded)
-      const float* src = P + (long)(k0 + kg * 8) * ld + min(r0 + col, R - 4);
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(src + (long)kk * ld);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[4 * kk + j] = a[j];
-      }
-    }
-  }
-}
-
-// registers -> bf16 LDS image of the tile (16-B chunks of 8 k, swizzled)
-template <bool KC>
-__device__ __forceinline__ void store_tile(char* base, const float (&v)[32]) {
-  const int t = threadIdx.x;
-  if (KC) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int u = i * kT + t, row = u >> 3, c = u & 7;
-      const u32x4 w{pack2(v[8 * i], v[8 * i + 1]), pack2(v[8 * i + 2], v[8 * i + 3]),
-                    pack2(v[8 * i + 4], v[8 * i + 5]), pack2(v[8 * i + 6], v[8 * i + 7])};
-      *reinterpret_cast<u32x4*>(base + row * kRowB + ((c ^ swz(row)) * 16)) = w;
-    }
-  } else {
-    const int kg = t & 7, col = (t >> 3) * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = col + j;
-      const u32x4 w{pack2(v[j], v[4 + j]), pack2(v[8 + j], v[12 + j]),
-                    pack2(v[16 + j], v[20 + j]), pack2(v[24 + j], v[28 + j])};
-      *reinterpret_cast<u32x4*>(base + row * kRowB + ((kg ^ swz(row)) * 16)) = w;
-    }
-  }
-}
 
 template <bool AKC, bool BKC, bool GUARD>
 __global__ __launch_bounds__(kT) void gemm_bf16_kernel(BParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = w >> 1, wn = w & 1;
-  const int h = lane >> 5, l31 = lane & 31;
   const int z = blockIdx.x / p.tiles_mn, t = blockIdx.x % p.tiles_mn;
   const int m0 = (t / p.tiles_n) * kBM, n0 = (t % p.tiles_n) * kBN;
-  const int kb = z * p.kps;
-  const int ke = min(p.K, kb + p.kps);
-  const int nk = (ke - kb + kBK - 1) / kBK;
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[f][g][r] = 0.f;
-
-  float va[32], vb[32];
-  load_tile<AKC, GUARD>(p.A, p.lda, p.M, m0, kb, ke, va);
-  load_tile<BKC, GUARD>(p.B, p.ldb, p.N, n0, kb, ke, vb);
-  store_tile<AKC>(smem, va);
-  store_tile<BKC>(smem + kOpB, vb);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const bool more = kt + 1 < nk;
-    if (more) {  // the next tile's global loads fly behind this tile's MFMAs
-      load_tile<AKC, GUARD>(p.A, p.lda, p.M, m0, kb + (kt + 1) * kBK, ke, va);
-      load_tile<BKC, GUARD>(p.B, p.ldb, p.N, n0, kb + (kt + 1) * kBK, ke, vb);
-    }
-    const char* sa = smem + (kt & 1) * kStageB;
-    const char* sb = sa + kOpB;
-#pragma unroll
-    for (int s = 0; s < kBK / 16; ++s) {
-      bf8 a[2], b[2];
-#pragma unroll
-      for (int f = 0; f < 2; ++f) {
-        const int ra = wm * 64 + f * 32 + l31, rb = wn * 64 + f * 32 + l31;
-        a[f] = *reinterpret_cast<const bf8*>(sa + ra * kRowB + (((2 * s + h) ^ swz(ra)) * 16));
-        b[f] = *reinterpret_cast<const bf8*>(sb + rb * kRowB + (((2 * s + h) ^ swz(rb)) * 16));
-      }
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-          acc[f][g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[f], b[g], acc[f][g], 0, 0, 0);
-    }
-    if (more) {
-      // the other stage: every wave left it at the barrier that ended the previous iteration
-      char* st = smem + ((kt + 1) & 1) * kStageB;
-      store_tile<AKC>(st, va);
-      store_tile<BKC>(st + kOpB, vb);
-    }
-    __syncthreads();
-  }
-
-  // MFMA 32x32 layout: acc[r] is row (r & 3) + 8 (r >> 2) + 4 h, column l31 of the tile
-  float* ws = p.ws + (long)z * p.M * p.N;
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const int col = n0 + wn * 64 + g * 32 + l31;
-      if (col >= p.N) continue;
-      const float bias = (p.splits == 1 && p.bias) ? p.bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 64 + f * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (row >= p.M) continue;
-        float v = acc[f][g][r];
-        if (p.splits > 1) {
-          ws[(long)row * p.N + col] = v;
-          continue;
-        }
-        float* c = p.C + (long)row * p.ldc + col;
-        v += bias;
-        if (p.beta) v += *c;
-        if (p.relu) v = fmaxf(v, 0.f);
-        if (p.gate) v = p.gate[(long)row * p.ldg + col] > 0.f ? v : 0.f;
-        *c = v;
-      }
-    }
+  constexpr int MODE = GUARD ? kLoadGuard : kLoadFast;
+  const DenseSrc<AKC, MODE> sa{p.A, p.lda, p.M, m0};
+  const DenseSrc<BKC, MODE> sb{p.B, p.ldb, p.N, n0};
+  tile_body(p, sa, sb, smem, m0, n0, z);
 }
 
 // C = epilogue(ws[0] + ws[1] + ... + ws[splits - 1]): the partial sums are added in index order
@@ -307,22 +125,16 @@ void launch_layout(const BParams& p, bool akc, bool bkc, int nblocks, hipStream_
 
 }  // namespace
 
+void bf16t::bf16_reduce(const BParams& p, hipStream_t s) {
+  const long n = (long)p.M * p.N;
+  hipLaunchKernelGGL(bf16_reduce_kernel, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, s, p);
+}
+
 GemmBf16Plan gemm_bf16_plan(const GemmBf16Args& a, int num_cus) {
   GemmBf16Plan plan;
   plan.guarded = !(a.K % kBK == 0 && operand_fast(a.A, a.lda, a.M, a.a_kcontig) &&
                    operand_fast(a.B, a.ldb, a.N, a.b_kcontig));
-  const long tiles = (long)ceil_div(a.M, kBM) * ceil_div(a.N, kBN);
-  // two workgroups per CU (64 KiB of LDS each); split-K when the tile grid alone leaves CUs idle,
-  // with at least two K tiles per split
-  int splits = 1;
-  if (tiles < num_cus) {
-    const int want = (int)((2L * num_cus + tiles - 1) / tiles);
-    const int kmax = a.K / (2 * kBK);
-    splits = want < kmax ? want : kmax;
-    if (splits > 32) splits = 32;  // bounds the partial-sum traffic of the combine
-    if (splits < 1) splits = 1;
-  }
-  const int kps = ceil_div(ceil_div(a.K, splits), kBK) * kBK;
+  const int kps = split_k(a.M, a.N, a.K, num_cus);
   plan.k_per_split = kps;
   plan.splits = ceil_div(a.K, kps);
   plan.ws_floats = plan.splits > 1 ? (long)plan.splits * a.M * a.N : 0;
@@ -350,10 +162,7 @@ void gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
   const int nblocks = p.tiles_mn * plan.splits;
   if (plan.guarded) launch_layout<true>(p, a.a_kcontig, a.b_kcontig, nblocks, s);
   else launch_layout<false>(p, a.a_kcontig, a.b_kcontig, nblocks, s);
-  if (plan.splits > 1) {
-    const long n = (long)a.M * a.N;
-    hipLaunchKernelGGL(bf16_reduce_kernel, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, s, p);
-  }
+  if (plan.splits > 1) bf16_reduce(p, s);
   if (a.rowsum) {
     if (a.a_kcontig)
       hipLaunchKernelGGL(bf16_rowsum_k_kernel, dim3(ceil_div(a.M, kT / 64)), dim3(kT), 0, s, a.A,

@@ -20,6 +20,20 @@ Fallback -- NCHW register-staged implicit GEMM (``csrc/conv.hip``) for shapes th
 not take (channel counts not a multiple of 4 beyond the stem, non power-of-two strides in dgrad).
 CPU tensors run ``torch.nn.functional.conv2d`` (the oracle of the CPU tests).
 Groups and dilation are not supported (no model here uses them).
+
+Mixed precision -- inside ``tdp.autocast`` (ops/precision.py) a float32 convolution the NHWC
+path takes runs its three passes on ``csrc/conv_bf16.hip``: the same implicit GEMMs with every
+operand element rounded once to bf16 (round-to-nearest-even), exact products, fp32 accumulation
+and fp32 tensors in memory. The ReLU mask and the bias gradient come from the unrounded output
+gradient (``relu_bias_bwd``); its result is what the two gradient GEMMs round. The op family is
+chosen in forward and the backward follows it. The stem padding, the weight-gradient
+destination, the stride phases and the shared-gradient sink are the fp32 path's own code
+(``_ConvNHWCFn`` with ``bf16=True``). Under autocast the GEMM epilogue does not produce the
+BatchNorm statistics (``bn_stats``): BatchNorm runs its own moments pass; a statistics epilogue
+for the bf16 kernel is a follow-up. Shapes the NHWC path does not take (see Fallback) stay
+fp32 under autocast, bitwise equal to the result outside it. CPU tensors under autocast run the
+same contract in torch math (``_ConvBf16CpuFn``). ``AUTOCAST_FP32_CONV = True`` keeps every
+convolution fp32 under autocast (A/B measurement).
 """
 from __future__ import annotations
 
@@ -29,6 +43,7 @@ import torch.nn.functional as F
 from .._native import native
 from . import plan_db
 from ._grad import SharedGrad, grad_dest, needs
+from .precision import is_autocast_enabled
 
 
 def _pair(v):
@@ -110,7 +125,9 @@ class _ConvNHWCFn(torch.autograd.Function):
     the RGB stem (3 channels, padded to 4 for the 16-B DMA chunks) repacks, natively."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, relu: bool, sink=None, stats_box=None):
+    def forward(ctx, x, weight, bias, stride, padding, relu: bool, sink=None, stats_box=None,
+                bf16: bool = False):
+        # bf16: every GEMM of the three passes on the mixed-precision kernels (csrc/conv_bf16.hip)
         C = native()
         N, Cin, H, W = x.shape
         Cout, _, R, S = weight.shape
@@ -119,7 +136,12 @@ class _ConvNHWCFn(torch.autograd.Function):
         ph, pw = padding
         xp = _as_cl(C, x, Cp)
         wt = _as_cl(C, weight, Cp)  # the parameter itself for every conv but the stem
-        if stats_box is not None and bias is None and not relu:
+        if bf16:
+            if stats_box is not None:
+                stats_box.append(None)  # no statistics epilogue: BatchNorm takes its own moments
+            y = C.conv_nhwc_fwd(xp, wt.permute(0, 2, 3, 1), bias, R, S, sh, sw, ph, pw, relu,
+                                bf16=True)
+        elif stats_box is not None and bias is None and not relu:
             # the GEMM epilogue also emits the output's per-tile BN statistics (or None)
             y, st = C.conv_nhwc_fwd_stats(xp, wt.permute(0, 2, 3, 1), R, S, sh, sw, ph, pw)
             stats_box.append(st)
@@ -128,6 +150,7 @@ class _ConvNHWCFn(torch.autograd.Function):
         ctx.geom = (R, S, sh, sw, ph, pw, Cin, Cp)
         ctx.sink = sink
         ctx.relu = relu
+        ctx.bf16 = bf16
         ctx.params = (weight, bias)
         ctx.save_for_backward(xp, wt, y if relu else None)
         return y
@@ -139,6 +162,7 @@ class _ConvNHWCFn(torch.autograd.Function):
         w_param, b_param = ctx.params
         R, S, sh, sw, ph, pw, Cin, Cp = ctx.geom
         Cout = wt.shape[0]
+        bf16 = ctx.bf16
         dy = _as_cl(C, dy)
         want_db = b_param is not None and needs(ctx, 2)
         db = grad_dest(b_param) if want_db else None
@@ -151,17 +175,18 @@ class _ConvNHWCFn(torch.autograd.Function):
         dx = dw = None
         if needs(ctx, 1):
             dw = grad_dest(w_param)
-            if C.conv_wgrad_transposed(Cout, R, S, Cp):
+            if not bf16 and C.conv_wgrad_transposed(Cout, R, S, Cp):
                 # dW^T [(r,s,c)][co] when it pads the 128-row MFMA tiles less (small Cout, Cout=192)
                 dwT = torch.empty((R, S, Cp, Cout), device=dy.device, dtype=dy.dtype)
                 C.conv_nhwc_wgrad(g, xp, dwT, R, S, sh, sw, ph, pw, 0.0)
                 C.copy4d(dw, dwT.permute(3, 2, 0, 1))
             elif Cp == Cin and dw.permute(0, 2, 3, 1).is_contiguous():
                 # straight into the gradient slot ([Cout][R][S][C] = the parameter's layout)
-                C.conv_nhwc_wgrad(g, xp, dw.permute(0, 2, 3, 1), R, S, sh, sw, ph, pw, 0.0)
+                C.conv_nhwc_wgrad(g, xp, dw.permute(0, 2, 3, 1), R, S, sh, sw, ph, pw, 0.0,
+                                  bf16=bf16)
             else:
                 dwt = torch.empty((Cout, R, S, Cp), device=dy.device, dtype=dy.dtype)
-                C.conv_nhwc_wgrad(g, xp, dwt, R, S, sh, sw, ph, pw, 0.0)
+                C.conv_nhwc_wgrad(g, xp, dwt, R, S, sh, sw, ph, pw, 0.0, bf16=bf16)
                 C.copy4d(dw, dwt.permute(0, 3, 1, 2))
         if needs(ctx, 0):
             sink = ctx.sink
@@ -169,17 +194,17 @@ class _ConvNHWCFn(torch.autograd.Function):
             if sh == 1 and sw == 1:
                 # with a shared residual-input gradient: accumulated by the GEMM (beta = 1)
                 dx = C.conv_nhwc_dgrad_w(g, wt, list(xp.shape), sh, sw, ph, pw, out=acc,
-                                         beta=0.0 if acc is None else 1.0)
+                                         beta=0.0 if acc is None else 1.0, bf16=bf16)
             else:
-                dx = _dgrad_phases(C, g, wt, xp.shape, R, S, sh, sw, ph, pw, into=acc)
+                dx = _dgrad_phases(C, g, wt, xp.shape, R, S, sh, sw, ph, pw, into=acc, bf16=bf16)
             if Cp != Cin:
                 dx = dx[:, :Cin]
             if sink is not None:
                 dx = dx if acc is not None else sink.deposit(dx)
-        return dx, dw, db, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None
 
 
-def _dgrad_phases(C, g, wt, x_shape, R, S, sh, sw, ph, pw, into=None):
+def _dgrad_phases(C, g, wt, x_shape, R, S, sh, sw, ph, pw, into=None, bf16=False):
     """Strided input gradient as sh*sw stride-1 GEMMs, one per output phase.
 
     dx pixels h = a + sh*i only receive taps r = r0 + sh*t with r0 = (a + ph) mod sh, from dy row
@@ -206,11 +231,47 @@ def _dgrad_phases(C, g, wt, x_shape, R, S, sh, sw, ph, pw, into=None):
                     C.copy4d(view, none)  # no tap reaches this phase: zeros
                 continue
             C.copy4d(view, C.conv_nhwc_dgrad_phase_w(g, wt, Hp, Wp, Rp, Sp, da, db, r0, s0, sh,
-                                                     sw), accumulate=acc)
+                                                     sw, bf16=bf16), accumulate=acc)
     return dx
 
 
 FORCE_NCHW = False  # tests: route every conv through the NCHW fallback kernels
+AUTOCAST_FP32_CONV = False  # A/B measurement: convolutions stay fp32 inside tdp.autocast
+
+
+def _bf16r(t: torch.Tensor) -> torch.Tensor:
+    """``t`` with every element rounded to bf16 (round-to-nearest-even), as float32."""
+    return t.bfloat16().float()
+
+
+class _ConvBf16CpuFn(torch.autograd.Function):
+    """The bf16 contract of the device path in torch math (CPU tensors under autocast): each
+    pass rounds its operands once, the ReLU mask and the bias gradient use the unrounded g."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, relu: bool):
+        y = F.conv2d(_bf16r(x), _bf16r(weight), bias, stride, padding)
+        if relu:
+            y = F.relu(y)
+        ctx.geom = (stride, padding)
+        ctx.relu = relu
+        ctx.save_for_backward(x, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        stride, padding = ctx.geom
+        g = dy * (y > 0) if ctx.relu else dy
+        gr = _bf16r(g)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.nn.grad.conv2d_input(x.shape, _bf16r(weight), gr, stride, padding)
+        if ctx.needs_input_grad[1]:
+            dw = torch.nn.grad.conv2d_weight(_bf16r(x), weight.shape, gr, stride, padding)
+        if ctx.needs_input_grad[2]:
+            db = g.sum(dim=(0, 2, 3))
+        return dx, dw, db, None, None, None
 
 
 def _nhwc_ok(x, weight, stride):
@@ -230,9 +291,17 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     channels_last inputs). ``grad_into``: the input gradient goes into that shared buffer (a
     forked residual input, ops/_grad.py ``fork``). ``bn_stats``: the output will be
     batch-normalised -- the GEMM epilogue also computes its per-channel statistics, attached
-    to the result for ``batch_norm`` (no moments pass over the output)."""
+    to the result for ``batch_norm`` (no moments pass over the output).
+
+    Inside ``tdp.autocast`` a float32 convolution computes in bf16 mixed precision (operands
+    rounded once per pass, fp32 accumulation, fp32 tensors; see the module docstring). There
+    ``bn_stats`` produces nothing -- BatchNorm runs its own moments pass; a statistics epilogue
+    for the bf16 kernel is a follow-up -- and shapes the NHWC path does not take stay fp32."""
     stride, padding = _pair(stride), _pair(padding)
+    amp = is_autocast_enabled() and x.dtype == torch.float32 and not AUTOCAST_FP32_CONV
     if not x.is_cuda:
+        if amp:
+            return _ConvBf16CpuFn.apply(x, weight, bias, stride, padding, relu)
         y = F.conv2d(x, weight, bias, stride, padding)
         return F.relu(y) if relu else y
     if x.dtype != torch.float32:
@@ -240,7 +309,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     if _nhwc_ok(x, weight, stride):
         plan_db.ensure_loaded(native())  # measured per-geometry plans (ops/plan_db.py)
         box = [] if bn_stats else None
-        y = _ConvNHWCFn.apply(x, weight, bias, stride, padding, relu, grad_into, box)
+        y = _ConvNHWCFn.apply(x, weight, bias, stride, padding, relu, grad_into, box, amp)
         if box and box[0] is not None:
             y._tdp_bn_part = (box[0], y._version)  # ops/norm.py batch_norm consumes it
         return y
