@@ -1287,6 +1287,108 @@ std::vector<int64_t> conv_bf16_plan_op(int64_t mode, std::vector<int64_t> x_shap
   return {pl.splits, pl.k_per_split};
 }
 
+// ------------------------------------------------ grouped / depthwise convolution (conv_grouped.hip)
+// w: the parameter [Cout, Cg, R, S] in channels_last memory
+GroupConvGeom group_geom(const std::vector<int64_t>& xs, const Tensor& w, int64_t sh, int64_t sw,
+                         int64_t ph, int64_t pw, int64_t groups) {
+  check_weight_cl(w);
+  TORCH_CHECK(xs.size() == 4, "conv (grouped): 4-D input expected");
+  TORCH_CHECK(groups > 1 && xs[1] % groups == 0 && w.size(0) % groups == 0 &&
+                  w.size(1) == xs[1] / groups,
+              "conv (grouped): input channels, weight shape and groups disagree");
+  TORCH_CHECK(sh > 0 && sw > 0 && ph >= 0 && pw >= 0, "conv (grouped): stride / padding");
+  GroupConvGeom g{(int)xs[0], (int)xs[1], (int)xs[2], (int)xs[3], (int)w.size(0), (int)w.size(2),
+                  (int)w.size(3), (int)sh, (int)sw, (int)ph, (int)pw, (int)groups};
+  TORCH_CHECK(conv_group_family(g) != kGroupNone,
+              "conv (grouped): channels per group must be multiples of 4, or 1 (depthwise) "
+              "with input channels a multiple of 4");
+  const int64_t P = (g.H + 2 * g.ph - g.R) / g.sh + 1, Q = (g.W + 2 * g.pw - g.S) / g.sw + 1;
+  TORCH_CHECK(g.H + 2 * g.ph >= g.R && g.W + 2 * g.pw >= g.S && P > 0 && Q > 0,
+              "conv (grouped): empty output");
+  TORCH_CHECK((long)g.N * g.C * g.H * g.W < (1L << 31) && (long)g.N * g.Cout * P * Q < (1L << 31),
+              "conv (grouped): tensors must have < 2^31 elements");
+  return g;
+}
+
+void check_aligned16(const Tensor& t, const char* what) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, " must be 16-B aligned");
+}
+
+void check_group_dy(const Tensor& dy, const GroupConvGeom& g) {
+  CHECK_GPU(dy); CHECK_F32(dy); CHECK_CL(dy);
+  check_aligned16(dy, "conv (grouped): dy");
+  TORCH_CHECK(dy.size(0) == g.N && dy.size(1) == g.Cout &&
+                  dy.size(2) == (g.H + 2 * g.ph - g.R) / g.sh + 1 &&
+                  dy.size(3) == (g.W + 2 * g.pw - g.S) / g.sw + 1,
+              "conv (grouped): dy shape");
+}
+
+Tensor conv_grouped_fwd_op(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias,
+                           int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t groups,
+                           bool relu) {
+  CHECK_GPU(x); CHECK_F32(x); CHECK_CL(x);
+  const GroupConvGeom g = group_geom(x.sizes().vec(), w, sh, sw, ph, pw, groups);
+  check_aligned16(x, "conv (grouped): x"); check_aligned16(w, "conv (grouped): weight");
+  const float* bp = opt_vec(bias, g.Cout, "conv (grouped): bias");
+  if (bp != nullptr) check_aligned16(*bias, "conv (grouped): bias");
+  auto y = at::empty({g.N, g.Cout, (g.H + 2 * g.ph - g.R) / g.sh + 1,
+                      (g.W + 2 * g.pw - g.S) / g.sw + 1},
+                     x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  conv_grouped_fwd(g, x.data_ptr<float>(), w.data_ptr<float>(), bp, relu, y.data_ptr<float>(),
+                   cur_stream());
+  return y;
+}
+
+// with `out`: written there, out = dgrad (+ out when accumulate)
+Tensor conv_grouped_dgrad_op(const Tensor& dy, const Tensor& w, std::vector<int64_t> x_shape,
+                             int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t groups,
+                             const c10::optional<Tensor>& out, bool accumulate) {
+  const GroupConvGeom g = group_geom(x_shape, w, sh, sw, ph, pw, groups);
+  check_group_dy(dy, g);
+  check_aligned16(w, "conv (grouped): weight");
+  Tensor dx;
+  if (out.has_value() && out->defined()) {
+    dx = *out;
+    CHECK_GPU(dx); CHECK_F32(dx); CHECK_CL(dx);
+    TORCH_CHECK(dx.sizes().vec() == x_shape, "conv (grouped) dgrad: out shape");
+  } else {
+    TORCH_CHECK(!accumulate, "conv (grouped) dgrad: accumulate needs out");
+    dx = at::empty(x_shape, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+  }
+  check_aligned16(dx, "conv (grouped): dx");
+  conv_grouped_dgrad(g, dy.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(),
+                     accumulate, cur_stream());
+  return dx;
+}
+
+// dw: [Cout, Cg, R, S] in channels_last memory (the parameter's gradient slot), overwritten
+void conv_grouped_wgrad_op(const Tensor& dy, const Tensor& x, Tensor& dw, int64_t sh, int64_t sw,
+                           int64_t ph, int64_t pw, int64_t groups) {
+  CHECK_GPU(x); CHECK_F32(x); CHECK_CL(x);
+  const GroupConvGeom g = group_geom(x.sizes().vec(), dw, sh, sw, ph, pw, groups);
+  check_group_dy(dy, g);
+  check_aligned16(x, "conv (grouped): x"); check_aligned16(dw, "conv (grouped): dw");
+  const GroupConvPlan pl = conv_grouped_wgrad_plan(g, num_cus(dw.get_device()));
+  Tensor ws;
+  if (pl.ws_floats > 0) ws = at::empty({pl.ws_floats}, dy.options());
+  conv_grouped_wgrad(g, pl, dy.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
+                     pl.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, cur_stream());
+}
+
+// {splits, k_per_split} of the weight gradient's plan (the N*P*Q reduction's ranges)
+std::vector<int64_t> conv_grouped_wgrad_plan_op(std::vector<int64_t> x_shape, int64_t cout,
+                                                int64_t R, int64_t S, int64_t sh, int64_t sw,
+                                                int64_t ph, int64_t pw, int64_t groups) {
+  TORCH_CHECK(x_shape.size() == 4 && groups > 0 && sh > 0 && sw > 0, "conv_grouped_wgrad_plan");
+  const GroupConvGeom g{(int)x_shape[0], (int)x_shape[1], (int)x_shape[2], (int)x_shape[3],
+                        (int)cout, (int)R, (int)S, (int)sh, (int)sw, (int)ph, (int)pw,
+                        (int)groups};
+  TORCH_CHECK(conv_group_family(g) != kGroupNone, "conv_grouped_wgrad_plan: unsupported shape");
+  const GroupConvPlan pl =
+      conv_grouped_wgrad_plan(g, num_cus((int)c10::hip::current_device()));
+  return {pl.splits, pl.k_per_split};
+}
+
 // NHWC pooling: x channels_last -> y channels_last
 std::vector<Tensor> maxpool_nhwc_fwd_op(const Tensor& x, int64_t k, int64_t s, int64_t pad) {
   CHECK_GPU(x); CHECK_F32(x); CHECK_CL(x);
@@ -1996,6 +2098,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_bf16_plan", &conv_bf16_plan_op, py::arg("mode"), py::arg("x_shape"),
         py::arg("cout"), py::arg("R"), py::arg("S"), py::arg("sh"), py::arg("sw"), py::arg("ph"),
         py::arg("pw"));
+  // grouped / depthwise convolution (conv_grouped.hip), fp32
+  m.def("conv_grouped_fwd", &conv_grouped_fwd_op, py::arg("x"), py::arg("w"), py::arg("bias"),
+        py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("groups"),
+        py::arg("relu") = false);
+  m.def("conv_grouped_dgrad", &conv_grouped_dgrad_op, py::arg("dy"), py::arg("w"),
+        py::arg("x_shape"), py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"),
+        py::arg("groups"), py::arg("out") = py::none(), py::arg("accumulate") = false);
+  m.def("conv_grouped_wgrad", &conv_grouped_wgrad_op, py::arg("dy"), py::arg("x"),
+        py::arg("dw"), py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"),
+        py::arg("groups"));
+  m.def("conv_grouped_wgrad_plan", &conv_grouped_wgrad_plan_op, py::arg("x_shape"),
+        py::arg("cout"), py::arg("R"), py::arg("S"), py::arg("sh"), py::arg("sw"), py::arg("ph"),
+        py::arg("pw"), py::arg("groups"));
   m.def("copy4d", &copy4d_op, py::arg("dst"), py::arg("src"), py::arg("accumulate") = false);
   m.def("conv_wgrad_transposed", [](int64_t cout, int64_t R, int64_t S, int64_t C) {
     ConvGeom g{};

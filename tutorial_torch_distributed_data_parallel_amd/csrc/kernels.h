@@ -203,6 +203,36 @@ void splitk_reduce(const float* ws, int splits, int M, int N, void* C, bool c_bf
                    const float* gate = nullptr, long ldgate = 0);
 
 // ------------------------------------------------------------------------------------------------
+// Grouped / depthwise convolution (conv_grouped.hip): NHWC fp32 tensors, fp32 FMA on the VALU.
+//   x [N][H][W][C], w [Cout][R][S][Cg] (the parameter's channels_last memory, Cg = C / groups),
+//   y [N][P][Q][Cout]. Two families, by (C, Cout, groups):
+//     grouped    Cg > 1, Cg % 4 == 0 and Kg = Cout / groups % 4 == 0
+//     depthwise  Cg == 1 (Cout = m * C, channel multiplier m >= 1) and C % 4 == 0
+//   Any R, S, stride and zero padding; no dilation. All pointers 16-B aligned. Every pass is
+//   bitwise reproducible (no atomics; split weight gradients combine in a fixed order).
+// ------------------------------------------------------------------------------------------------
+constexpr int kGroupNone = 0, kGroupGrouped = 1, kGroupDepthwise = 2;
+struct GroupConvGeom {
+  int N, C, H, W, Cout, R, S, sh, sw, ph, pw, groups;
+};
+struct GroupConvPlan {
+  int splits = 1;       // ranges of the N*P*Q reduction of the weight gradient
+  int k_per_split = 0;  // pixels per range
+  long ws_floats = 0;   // workspace for the partials (0 when splits == 1)
+};
+int conv_group_family(const GroupConvGeom& g);  // kGroupNone: neither family takes the shape
+// y = relu?(conv(x, w) + bias)
+void conv_grouped_fwd(const GroupConvGeom& g, const float* x, const float* w, const float* bias,
+                      bool relu, float* y, hipStream_t s);
+// dx = conv^T(dy, w) (+ dx when accumulate); strided gradients gather directly
+void conv_grouped_dgrad(const GroupConvGeom& g, const float* dy, const float* w, float* dx,
+                        bool accumulate, hipStream_t s);
+GroupConvPlan conv_grouped_wgrad_plan(const GroupConvGeom& g, int num_cus);
+// dw [Cout][R][S][Cg] = sum over (n, p, q) of dy x shifted x; ws: pl.ws_floats floats
+void conv_grouped_wgrad(const GroupConvGeom& g, const GroupConvPlan& pl, const float* dy,
+                        const float* x, float* dw, float* ws, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Loss / metrics
 // ------------------------------------------------------------------------------------------------
 // Fused cross-entropy forward over logits[B,C] (fp32), int64 labels.

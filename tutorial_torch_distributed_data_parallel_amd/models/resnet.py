@@ -1,4 +1,6 @@
-"""ResNet-50 (torchvision v1.5 topology) -- BASELINE.json config "ResNet-50-sized CNN DDP 8x".
+"""ResNet-50 (torchvision v1.5 topology) -- BASELINE.json config "ResNet-50-sized CNN DDP 8x" --
+and ResNeXt-50 32x4d, the same network with a grouped 3x3 (``Bottleneck(groups=, base_width=)``,
+csrc/conv_grouped.hip).
 
 ``state_dict`` keys match ``torchvision.models.resnet50`` (conv1/bn1/layer1-4/fc, Bottleneck
 conv1-3/bn1-3/downsample.{0,1}); stride sits on the 3x3 conv (v1.5). 25.6 M parameters in 161
@@ -20,14 +22,17 @@ from ..nn import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Linear, MaxPool2d
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, device=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, device=None, groups=1,
+                 base_width=64):
         super().__init__()
         kw = dict(bias=False, device=device)
-        self.conv1 = Conv2d(inplanes, planes, 1, **kw)
-        self.bn1 = BatchNorm2d(planes, relu=True, device=device)
-        self.conv2 = Conv2d(planes, planes, 3, stride=stride, padding=1, **kw)
-        self.bn2 = BatchNorm2d(planes, relu=True, device=device)
-        self.conv3 = Conv2d(planes, planes * 4, 1, **kw)
+        # torchvision's width rule: ResNeXt widens the 3x3 and splits it into groups
+        width = int(planes * base_width / 64) * groups
+        self.conv1 = Conv2d(inplanes, width, 1, **kw)
+        self.bn1 = BatchNorm2d(width, relu=True, device=device)
+        self.conv2 = Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, **kw)
+        self.bn2 = BatchNorm2d(width, relu=True, device=device)
+        self.conv3 = Conv2d(width, planes * 4, 1, **kw)
         self.bn3 = BatchNorm2d(planes * 4, device=device)
         self.downsample = downsample
         self.stride = stride
@@ -71,9 +76,11 @@ def _takes_sink(m) -> bool:
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers=(3, 4, 6, 3), num_classes: int = 10, device=None):
+    def __init__(self, layers=(3, 4, 6, 3), num_classes: int = 10, device=None, groups=1,
+                 width_per_group=64):
         super().__init__()
         self.inplanes = 64
+        self.groups, self.base_width = groups, width_per_group
         self.conv1 = Conv2d(3, 64, 7, stride=2, padding=3, bias=False, device=device)
         self.bn1 = BatchNorm2d(64, relu=True, device=device)
         self.maxpool = MaxPool2d(kernel_size=3, stride=2, padding=1)
@@ -104,10 +111,11 @@ class ResNet(nn.Module):
             downsample = nn.Sequential(
                 Conv2d(self.inplanes, planes * 4, 1, stride=stride, bias=False, device=device),
                 BatchNorm2d(planes * 4, device=device))
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample, device)]
+        kw = dict(device=device, groups=self.groups, base_width=self.base_width)
+        layers = [Bottleneck(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * 4
         for _ in range(1, blocks):
-            layers.append(Bottleneck(self.inplanes, planes, device=device))
+            layers.append(Bottleneck(self.inplanes, planes, **kw))
         return nn.Sequential(*layers)
 
     def forward(self, x):
@@ -119,3 +127,10 @@ class ResNet(nn.Module):
 
 def resnet50(num_classes: int = 10, device=None) -> ResNet:
     return ResNet((3, 4, 6, 3), num_classes=num_classes, device=device)
+
+
+def resnext50_32x4d(num_classes: int = 10, device=None) -> ResNet:
+    """ResNeXt-50 32x4d (torchvision topology and state_dict keys): ResNet-50's block with a
+    32-group 3x3 of 4 channels per group at layer1, doubling per stage."""
+    return ResNet((3, 4, 6, 3), num_classes=num_classes, device=device, groups=32,
+                  width_per_group=4)

@@ -28,26 +28,37 @@ class Linear(nn.Linear):
 
 
 class Conv2d(nn.Conv2d):
-    """``nn.Conv2d`` (groups=1, dilation=1, zero padding) on the implicit-GEMM kernels, with an
-    optional fused ReLU."""
+    """``nn.Conv2d`` (dilation=1, zero padding) on the implicit-GEMM kernels, with an optional
+    fused ReLU. ``groups > 1`` runs the grouped / depthwise kernels (``ops.conv2d``: channels per
+    group multiples of 4, or depthwise with ``in_channels % 4 == 0``)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0,
-                 bias: bool = True, relu: bool = False, device=None, dtype=None):
+                 bias: bool = True, relu: bool = False, device=None, dtype=None,
+                 groups: int = 1, dilation=1):
+        if tuple(nn.modules.utils._pair(dilation)) != (1, 1):
+            raise NotImplementedError("Conv2d: dilation is not supported (dilation must be 1)")
+        if groups != 1 and device is not None and torch.device(device).type == "cuda":
+            # the channel combinations the GPU kernels take: refuse the others here, not at the
+            # first forward (a CPU module runs any combination through torch)
+            ops.conv.grouped_family(in_channels, out_channels, groups)
         super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding,
-                         bias=bias, device=device, dtype=dtype)
+                         groups=groups, bias=bias, device=device, dtype=dtype)
         self.relu = relu
         self.bn_stats = False  # output feeds a BatchNorm: emit its statistics (ops.conv2d)
         # The weight lives in channels_last memory ([Cout][R][S][C]): exactly the operand layout
         # of the implicit-GEMM kernels (forward B, input-gradient taps, weight-gradient output),
         # so no step permutes or copies it. Shape and state_dict keys stay torch's [Cout, C, R, S].
-        if in_channels % 4 == 0:
+        # (Cg = in_channels / groups: the weight's channel extent.)
+        if (in_channels // groups) % 4 == 0:
             self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
 
     def forward(self, x, grad_into=None):
         return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding, relu=self.relu,
-                          grad_into=grad_into, bn_stats=self.bn_stats and self.training)
+                          grad_into=grad_into, bn_stats=self.bn_stats and self.training,
+                          groups=self.groups)
 
     def extra_repr(self) -> str:
+        # torch's extra_repr shows groups when it is not 1
         return super().extra_repr() + (", relu=True" if self.relu else "")
 
 

@@ -19,7 +19,16 @@ Main path -- channels_last (NHWC) activations on the LDS-DMA MFMA GEMM pipeline
 Fallback -- NCHW register-staged implicit GEMM (``csrc/conv.hip``) for shapes the NHWC path does
 not take (channel counts not a multiple of 4 beyond the stem, non power-of-two strides in dgrad).
 CPU tensors run ``torch.nn.functional.conv2d`` (the oracle of the CPU tests).
-Groups and dilation are not supported (no model here uses them).
+Dilation is not supported (no model here uses it).
+
+Groups -- ``groups > 1`` runs ``csrc/conv_grouped.hip`` (``_ConvGroupedFn``): NHWC, fp32 FMA on the
+VALU, the same channels_last weight memory in all three passes, the weight gradient written
+straight into the parameter's gradient slot. Two families: grouped (Cin/groups and Cout/groups
+multiples of 4; ResNeXt, two-tower AlexNet) and depthwise (groups == Cin, Cout = m * Cin,
+Cin % 4 == 0; a register-tap stencil). Any other channel combination raises
+``NotImplementedError``. No statistics epilogue (``bn_stats`` produces nothing) and no bf16 form:
+inside ``tdp.autocast`` a grouped convolution stays fp32, bitwise equal to the result outside it.
+``groups == 1`` never reaches this code.
 
 Mixed precision -- inside ``tdp.autocast`` (ops/precision.py) a float32 convolution the NHWC
 path takes runs its three passes on ``csrc/conv_bf16.hip``: the same implicit GEMMs with every
@@ -274,6 +283,82 @@ class _ConvBf16CpuFn(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+GROUPS_RULE = (
+    "native grouped convolution takes (a) grouped: groups > 1 with Cin/groups and Cout/groups "
+    "both multiples of 4, or (b) depthwise: groups == Cin (Cout = m * Cin, channel multiplier "
+    "m >= 1) with Cin a multiple of 4")
+
+
+def grouped_family(cin: int, cout: int, groups: int) -> str:
+    """``"grouped"`` or ``"depthwise"``: the kernel family of csrc/conv_grouped.hip that takes
+    ``(cin, cout, groups)``; any other combination raises ``NotImplementedError`` (there is no
+    slow path)."""
+    if groups < 1 or cin % groups or cout % groups:
+        raise ValueError(f"conv2d: Cin={cin} and Cout={cout} must be divisible by groups={groups}")
+    cg, kg = cin // groups, cout // groups
+    if groups > 1 and cg == 1 and cin % 4 == 0:
+        return "depthwise"
+    if groups > 1 and cg > 1 and cg % 4 == 0 and kg % 4 == 0:
+        return "grouped"
+    raise NotImplementedError(f"conv2d(Cin={cin}, Cout={cout}, groups={groups}): {GROUPS_RULE}")
+
+
+class _ConvGroupedFn(torch.autograd.Function):
+    """Grouped / depthwise convolution on csrc/conv_grouped.hip (fp32 FMA, NHWC). As in
+    ``_ConvNHWCFn`` the weight operand of all three passes is the parameter's own channels_last
+    memory ([Cout][R][S][Cg]) and the weight gradient is written straight into the parameter's
+    gradient slot; the ReLU mask and the bias gradient are the shared ``relu_bias_bwd`` pass."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, groups: int, relu: bool, sink=None):
+        C = native()
+        xc = _as_cl(C, x)
+        wt = _as_cl(C, weight)  # the parameter itself when it is stored channels_last
+        y = C.conv_grouped_fwd(xc, wt, bias, *stride, *padding, groups, relu)
+        ctx.geom = (*stride, *padding, groups)
+        ctx.sink = sink
+        ctx.relu = relu
+        ctx.params = (weight, bias)
+        ctx.save_for_backward(xc, wt, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = native()
+        xc, wt, y = ctx.saved_tensors
+        w_param, b_param = ctx.params
+        geom = ctx.geom
+        Cout = wt.shape[0]
+        dy = _as_cl(C, dy)
+        want_db = b_param is not None and needs(ctx, 2)
+        db = grad_dest(b_param) if want_db else None
+        if ctx.relu or want_db:
+            g2 = C.relu_bias_bwd(_rows(dy), _rows(y) if ctx.relu else None, db)
+            g = g2.view(dy.shape[0], dy.shape[2], dy.shape[3], Cout).permute(0, 3, 1, 2)
+        else:
+            g = dy
+        dx = dw = None
+        if needs(ctx, 1):
+            dw = grad_dest(w_param)
+            if dw.permute(0, 2, 3, 1).is_contiguous():
+                C.conv_grouped_wgrad(g, xc, dw, *geom)  # straight into the gradient slot
+            else:
+                dwt = torch.empty_like(wt)
+                C.conv_grouped_wgrad(g, xc, dwt, *geom)
+                C.copy4d(dw, dwt)
+        if needs(ctx, 0):
+            sink = ctx.sink
+            acc = sink.buf if sink is not None else None
+            if acc is not None and not acc.is_contiguous(memory_format=_CL):
+                acc = None
+            # with a shared residual-input gradient: accumulated by the kernel's epilogue
+            dx = C.conv_grouped_dgrad(g, wt, list(xc.shape), *geom, out=acc,
+                                      accumulate=acc is not None)
+            if sink is not None and acc is None:
+                dx = sink.deposit(dx)
+        return dx, dw, db, None, None, None, None, None
+
+
 def _nhwc_ok(x, weight, stride):
     if FORCE_NCHW:
         return False
@@ -284,7 +369,8 @@ def _nhwc_ok(x, weight, stride):
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None,
            stride=1, padding=0, relu: bool = False,
-           grad_into: SharedGrad | None = None, bn_stats: bool = False) -> torch.Tensor:
+           grad_into: SharedGrad | None = None, bn_stats: bool = False,
+           groups: int = 1, dilation=1) -> torch.Tensor:
     """``relu?(conv2d(x, weight, bias, stride, padding))`` for float32 [N, C, H, W] tensors.
 
     On the GPU the result is channels_last (NHWC memory, logical NCHW shape, as torch does for
@@ -296,8 +382,23 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     Inside ``tdp.autocast`` a float32 convolution computes in bf16 mixed precision (operands
     rounded once per pass, fp32 accumulation, fp32 tensors; see the module docstring). There
     ``bn_stats`` produces nothing -- BatchNorm runs its own moments pass; a statistics epilogue
-    for the bf16 kernel is a follow-up -- and shapes the NHWC path does not take stay fp32."""
+    for the bf16 kernel is a follow-up -- and shapes the NHWC path does not take stay fp32.
+
+    ``groups > 1``: grouped or depthwise convolution on csrc/conv_grouped.hip (``weight`` is
+    torch's ``[Cout, Cin/groups, R, S]``); ``grouped_family`` states which channel counts are
+    taken, any other raises ``NotImplementedError``. ``bn_stats`` produces nothing there and the
+    convolution stays fp32 inside ``tdp.autocast``. ``dilation`` other than 1 is not supported."""
     stride, padding = _pair(stride), _pair(padding)
+    if _pair(dilation) != (1, 1):
+        raise NotImplementedError("conv2d: dilation is not supported (dilation must be 1)")
+    if groups != 1:
+        if not x.is_cuda:
+            y = F.conv2d(x, weight, bias, stride, padding, 1, groups)
+            return F.relu(y) if relu else y
+        if x.dtype != torch.float32:
+            raise TypeError(f"native conv2d expects float32 activations, got {x.dtype}")
+        grouped_family(x.shape[1], weight.shape[0], groups)
+        return _ConvGroupedFn.apply(x, weight, bias, stride, padding, groups, relu, grad_into)
     amp = is_autocast_enabled() and x.dtype == torch.float32 and not AUTOCAST_FP32_CONV
     if not x.is_cuda:
         if amp:

@@ -13,7 +13,9 @@ What stays fp32 under autocast: BatchNorm (which then runs its own moments pass:
 convolution has no statistics epilogue yet), pooling, dropout, the losses, the optimizers, and
 the convolutions the channels_last path does not take (channel counts that are not a multiple
 of 4 beyond the stem, non-power-of-two strides with an input gradient): those run the fp32 NCHW
-fallback, bitwise equal to the result outside autocast. ``ops.conv.AUTOCAST_FP32_CONV = True``
+fallback, bitwise equal to the result outside autocast. Grouped and depthwise convolutions
+(``groups > 1``, csrc/conv_grouped.hip) have no bf16 form and stay fp32 too, bitwise equal to the
+result outside autocast. ``ops.conv.AUTOCAST_FP32_CONV = True``
 keeps every convolution fp32 (A/B measurement).
 
 The op is chosen in forward, so a layer's backward follows its forward whether or not the flag
