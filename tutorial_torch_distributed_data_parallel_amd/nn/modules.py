@@ -177,6 +177,19 @@ class SyncBatchNorm(_NativeBN):
         return out
 
 
+class LayerNorm(nn.LayerNorm):
+    """``nn.LayerNorm`` through ``ops.layer_norm`` (CPU tensors; a GPU tensor raises: no kernel
+    yet)."""
+
+    def forward(self, x):
+        return ops.layer_norm(x, self.normalized_shape, self.weight, self.bias, self.eps)
+
+
+class GELU(nn.GELU):
+    def forward(self, x):
+        return ops.gelu(x, approximate=self.approximate)
+
+
 class CrossEntropyLoss(nn.CrossEntropyLoss):
     def forward(self, input, target):
         if self.weight is not None:
