@@ -269,6 +269,10 @@ class Accelerator:
         False when the model has no DDP (a CPU process) or the optimizer is not fusable."""
         d = self.ddp_of(model)
         opt = optimizer.optimizer if isinstance(optimizer, AcceleratedOptimizer) else optimizer
+        from ..optim.fused import _LayerwiseBase
+
+        if isinstance(opt, _LayerwiseBase):
+            return False  # LAMB / LARS need whole-tensor norms: they step after backward
         return bool(d is not None and d.register_fused_optimizer(opt))
 
     def prepare_optimizer(self, opt):

@@ -78,12 +78,18 @@ def _optimizer(t, params):
         return optim.SGD(params, lr=t["lr"], momentum=t["momentum"])
     if t["optimizer"].lower() == "adamw":
         return optim.AdamW(params, lr=t["lr"])
+    if t["optimizer"].lower() == "lamb":
+        return optim.LAMB(params, lr=t["lr"])
+    if t["optimizer"].lower() == "lars":
+        return optim.LARS(params, lr=t["lr"], momentum=t["momentum"])
     return optim.Adam(params, lr=t["lr"])
 
 
 def _want_fused(t, device) -> bool:
     from .utils.config import tristate
 
+    if str(t.get("optimizer", "")).lower() in ("lamb", "lars"):
+        return False  # per-tensor norms: the update cannot run inside the sharded reduction
     v = tristate(t.get("fused_optimizer"))
     return device.type == "cuda" if v is None else (v and device.type == "cuda")
 

@@ -680,6 +680,131 @@ void adam_multi_op(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs,
   adam_multi(reinterpret_cast<const TensorChunk*>(tab.data_ptr()), count, h, cur_stream());
 }
 
+// ---- layer-wise optimizers (optim_layerwise.hip): the work table, built once per layout.
+// It holds raw pointers the kernels write through, so it is built here from checked tensors
+// only, keeps them alive, and cannot be made or altered from Python.
+struct PyLwTable {
+  Tensor chunks, runs, tensors, partials;
+  std::vector<Tensor> keep;
+  int nchunks = 0, nruns = 0, ntensors = 0;
+  bool vec = true, has_s0 = false, has_s1 = false;
+};
+
+Tensor to_device_bytes(const void* src, size_t bytes, const at::Device& dev) {
+  auto host = at::empty({(int64_t)std::max<size_t>(bytes, 1)},
+                        at::TensorOptions().dtype(at::kByte).pinned_memory(true));
+  if (bytes) std::memcpy(host.data_ptr(), src, bytes);
+  auto out = host.to(dev, /*non_blocking=*/false);  // built once, outside any capture
+  return out;
+}
+
+std::shared_ptr<PyLwTable> layerwise_table(const std::vector<Tensor>& ps,
+                                           const std::vector<Tensor>& gs,
+                                           const std::vector<Tensor>& s0,
+                                           const std::vector<Tensor>& s1,
+                                           const std::vector<bool>& skip) {
+  TORCH_CHECK(!ps.empty(), "layerwise_table: no parameters");
+  TORCH_CHECK(skip.size() == ps.size(), "layerwise_table: one skip flag per parameter");
+  for (auto& t : ps) {
+    CHECK_GPU(t); CHECK_F32(t); CHECK_CONTIG(t);
+    TORCH_CHECK(t.device() == ps[0].device(), "layerwise_table: parameters on several devices");
+  }
+  check_list(gs, ps, "layerwise_table: gs");
+  if (!s0.empty()) check_list(s0, ps, "layerwise_table: s0");
+  if (!s1.empty()) check_list(s1, ps, "layerwise_table: s1");
+  auto tab = std::make_shared<PyLwTable>();
+  tab->has_s0 = !s0.empty();
+  tab->has_s1 = !s1.empty();
+  std::vector<LwChunk> chunks;
+  std::vector<LwTensor> tensors;
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  for (size_t i = 0; i < ps.size(); ++i) {
+    const long n = ps[i].numel();
+    LwTensor tt{(int)chunks.size(), 0, skip[i] ? 1 : 0, 0};
+    for (long o = 0; o < n; o += kLwChunk) {
+      LwChunk c;
+      c.p = ps[i].data_ptr<float>() + o;
+      c.g = gs[i].data_ptr<float>() + o;
+      c.s0 = s0.empty() ? nullptr : s0[i].data_ptr<float>() + o;
+      c.s1 = s1.empty() ? nullptr : s1[i].data_ptr<float>() + o;
+      c.n = (int)std::min<long>(kLwChunk, n - o);
+      c.tensor = (int)i;
+      c.skip = tt.skip;
+      c.pad = 0;
+      tab->vec = tab->vec && al16(c.p) && al16(c.g) && al16(c.s0) && al16(c.s1);
+      chunks.push_back(c);
+      ++tt.count;
+    }
+    tensors.push_back(tt);
+    TORCH_CHECK(chunks.size() < ((size_t)1 << 30), "layerwise_table: too many chunks");
+  }
+  // runs: a chunk longer than kLwSmall is a workgroup's own; shorter ones go kLwRunMax to a run
+  std::vector<LwRun> runs;
+  LwRun pend{0, 0};
+  for (int ci = 0; ci < (int)chunks.size(); ++ci) {
+    if (chunks[ci].n > kLwSmall) {
+      if (pend.count) runs.push_back(pend);
+      pend.count = 0;
+      runs.push_back(LwRun{ci, 1});
+      continue;
+    }
+    if (pend.count == 0) pend.first = ci;
+    if (++pend.count == kLwRunMax) {
+      runs.push_back(pend);
+      pend.count = 0;
+    }
+  }
+  if (pend.count) runs.push_back(pend);
+  const auto dev = ps[0].device();
+  tab->nchunks = (int)chunks.size();
+  tab->nruns = (int)runs.size();
+  tab->ntensors = (int)tensors.size();
+  tab->chunks = to_device_bytes(chunks.data(), chunks.size() * sizeof(LwChunk), dev);
+  tab->runs = to_device_bytes(runs.data(), runs.size() * sizeof(LwRun), dev);
+  tab->tensors = to_device_bytes(tensors.data(), tensors.size() * sizeof(LwTensor), dev);
+  tab->partials = at::zeros({std::max(1, 2 * tab->nchunks)}, ps[0].options());
+  for (auto* l : {&ps, &gs, &s0, &s1}) tab->keep.insert(tab->keep.end(), l->begin(), l->end());
+  return tab;
+}
+
+LwTable lw_view(const PyLwTable& t, Tensor& ws) {
+  CHECK_GPU(ws); CHECK_F32(ws); CHECK_CONTIG(ws);
+  TORCH_CHECK(ws.device() == t.partials.device(), "layerwise: workspace on another device");
+  TORCH_CHECK(ws.numel() == 3 * (int64_t)t.ntensors, "layerwise: workspace needs 3 floats per "
+              "tensor (", 3 * t.ntensors, "), has ", ws.numel());
+  return LwTable{reinterpret_cast<const LwChunk*>(t.chunks.data_ptr()),
+                 reinterpret_cast<const LwRun*>(t.runs.data_ptr()),
+                 reinterpret_cast<const LwTensor*>(t.tensors.data_ptr()),
+                 t.nchunks, t.nruns, t.ntensors, t.vec, t.partials.data_ptr<float>(),
+                 ws.data_ptr<float>()};
+}
+
+// One LAMB step over the table (stages: bit mask 1 stage 1, 2 finish, 4 stage 2). With `hyper`
+// the scalars and bias corrections come from the block (opt_step_begin(hyper, 2) first); without
+// it the corrections are formed from the fp32 betas, as opt_step_begin forms them.
+void lamb_layerwise_op(const std::shared_ptr<PyLwTable>& tab, Tensor& ws, double lr, double b1,
+                       double b2, double eps, double wd, bool maximize, int64_t step,
+                       double grad_scale, const c10::optional<Tensor>& hyper, int64_t stages) {
+  TORCH_CHECK(tab && tab->has_s0 && tab->has_s1, "lamb: the table needs exp_avg and exp_avg_sq");
+  const float fb1 = (float)b1, fb2 = (float)b2;
+  AdamHyper h{(float)lr, fb1, fb2, (float)eps, (float)wd, false, maximize, false,
+              (float)(1.0 - std::pow((double)fb1, (double)step)),
+              (float)std::sqrt(1.0 - std::pow((double)fb2, (double)step)), (float)grad_scale,
+              hyper_ptr(hyper)};
+  lamb_layerwise(lw_view(*tab, ws), h, (int)stages & 7, cur_stream());
+}
+
+void lars_layerwise_op(const std::shared_ptr<PyLwTable>& tab, Tensor& ws, double lr,
+                       double momentum, double dampening, double wd, bool nesterov,
+                       bool maximize, bool first_step, double trust, double eps,
+                       double grad_scale, const c10::optional<Tensor>& hyper, int64_t stages) {
+  TORCH_CHECK(tab, "lars: no table");
+  TORCH_CHECK(momentum == 0.0 || tab->has_s0, "lars: momentum needs the table's buffers");
+  SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, maximize,
+             first_step, (float)grad_scale, hyper_ptr(hyper)};
+  lars_layerwise(lw_view(*tab, ws), h, (float)trust, (float)eps, (int)stages & 7, cur_stream());
+}
+
 // g = dy*(y>0) (new tensor; dy itself when y is None), db (optional) = sum over rows of g
 Tensor relu_bias_bwd_op(const Tensor& dy, const c10::optional<Tensor>& y,
                         const c10::optional<Tensor>& db, double beta_db, double gscale) {
@@ -2075,6 +2200,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vmaxs"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
         py::arg("weight_decay"), py::arg("amsgrad"), py::arg("maximize"), py::arg("decoupled"),
         py::arg("step"), py::arg("grad_scale") = 1.0, py::arg("hyper") = py::none());
+  py::class_<PyLwTable, std::shared_ptr<PyLwTable>>(m, "LayerwiseTable")
+      .def_readonly("nchunks", &PyLwTable::nchunks)
+      .def_readonly("nruns", &PyLwTable::nruns)
+      .def_readonly("ntensors", &PyLwTable::ntensors)
+      .def_readonly("vec", &PyLwTable::vec)
+      .def_property_readonly("partials", [](const PyLwTable& t) { return t.partials; });
+  m.def("layerwise_table", &layerwise_table, py::arg("ps"), py::arg("gs"), py::arg("s0"),
+        py::arg("s1"), py::arg("skip"));
+  m.def("layerwise_consts", []() {
+    return py::dict(py::arg("chunk") = (int)kLwChunk, py::arg("small") = (int)kLwSmall,
+                    py::arg("run_max") = (int)kLwRunMax);
+  });
+  m.def("lamb_layerwise", &lamb_layerwise_op, py::arg("table"), py::arg("ws"), py::arg("lr"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("maximize"), py::arg("step"), py::arg("grad_scale") = 1.0,
+        py::arg("hyper") = py::none(), py::arg("stages") = 7);
+  m.def("lars_layerwise", &lars_layerwise_op, py::arg("table"), py::arg("ws"), py::arg("lr"),
+        py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"),
+        py::arg("maximize"), py::arg("first_step"), py::arg("trust_coefficient"),
+        py::arg("eps"), py::arg("grad_scale") = 1.0, py::arg("hyper") = py::none(),
+        py::arg("stages") = 7);
   m.def("scale_", &scale_op);
   m.def("cast_f32_bf16", &cast_f32_bf16_op);
   m.def("conv2d_fwd", &conv2d_fwd_op);

@@ -285,6 +285,46 @@ struct TensorChunk {
 void sgd_multi(const TensorChunk* table, int count, const SgdHyper& h, hipStream_t s);
 void adam_multi(const TensorChunk* table, int count, const AdamHyper& h, hipStream_t s);
 
+// Layer-wise adaptive optimizers (LAMB, LARS; optim_layerwise.hip): a norm reduction per
+// parameter tensor feeding an elementwise update, three launches and no host synchronisation.
+//   stage 1  every chunk's (sum p^2, sum u^2) -> partials[chunk]   (LAMB also advances m and v;
+//            LARS sums g'^2)
+//   finish   per tensor: partials added in a fixed order -> ws = [norm_p | norm_u | ratio], T each
+//   stage 2  the update, scaled by ratio[tensor]
+// The work table is built once per layout (bindings.cpp layerwise_table). A chunk never crosses
+// a tensor; a run is what one workgroup takes: one chunk longer than kLwSmall, reduced by the
+// whole workgroup, or up to kLwRunMax chunks of at most kLwSmall elements, one per wave in turn.
+// The summation shape of a chunk therefore depends on its length alone.
+constexpr int kLwChunk = 8192;
+constexpr int kLwSmall = 1024;
+constexpr int kLwRunMax = 16;
+struct LwChunk {
+  float* p;
+  const float* g;
+  float* s0;  // LAMB exp_avg | LARS momentum buffer (null without momentum)
+  float* s1;  // LAMB exp_avg_sq
+  int n;
+  int tensor;
+  int skip;   // skip_1d tensor: ratio 1, weight decay 0
+  int pad;
+};
+struct LwRun { int first, count; };
+struct LwTensor { int first, count, skip, pad; };  // its chunks, in element order
+struct LwTable {
+  const LwChunk* chunks;
+  const LwRun* runs;
+  const LwTensor* tensors;
+  int nchunks, nruns, ntensors;
+  bool vec;        // every chunk pointer is 16-byte aligned
+  float* partials; // 2 * nchunks
+  float* ws;       // 3 * ntensors
+};
+// `stages` is a bit mask (1 stage 1, 2 finish, 4 stage 2); 7 is one optimizer step.
+void lamb_layerwise(const LwTable& t, const AdamHyper& h, int stages, hipStream_t s);
+// eps and trust_coefficient of the ratio; eps comes from the hyper block (kHEps) when h.dev is set.
+void lars_layerwise(const LwTable& t, const SgdHyper& h, float trust, float eps, int stages,
+                    hipStream_t s);
+
 // elementwise helpers
 void scale_inplace(float* x, long n, float a, hipStream_t s);
 // ReLU backward + bias gradient in one pass over dy[B][N] (row stride ld):

@@ -1,4 +1,5 @@
-"""Fused optimizers (native single-pass kernels on GPU; torch semantics)."""
-from .fused import SGD, Adam, AdamW
+"""Fused optimizers (native single-pass kernels on GPU; torch semantics), and the layer-wise
+adaptive LAMB / LARS (three launches: per-tensor norms, then the update)."""
+from .fused import LAMB, LARS, SGD, Adam, AdamW
 
-__all__ = ["SGD", "Adam", "AdamW"]
+__all__ = ["SGD", "Adam", "AdamW", "LAMB", "LARS"]

@@ -13,6 +13,9 @@ load_state_dict, LR schedulers all work) whose ``step`` is:
 Semantics are torch's (TORCH/optim/sgd.py, TORCH/optim/adam.py): momentum buffer initialised to
 the first gradient, dampening, nesterov, maximize, L2 vs decoupled weight decay, amsgrad,
 bias-corrected Adam with a per-parameter step counter.
+
+LAMB and LARS (torch has neither; their docstrings are the specification) keep the same three
+paths, but a step is three launches: their update is not elementwise (``_LayerwiseBase``).
 """
 from __future__ import annotations
 
@@ -491,6 +494,349 @@ class Adam(_FusedBase):
                 vv = st["max_exp_avg_sq"]
             denom = (vv.sqrt() / bc2s).add_(g["eps"])
             p.addcdiv_(m, denom, value=-g["lr"] / bc1)
+
+
+def _f32(x) -> float:
+    """A hyper-parameter as the kernels hold it: rounded to fp32, widened back to a double."""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+class _LayerwiseBase(_FusedBase):
+    """What LAMB and LARS share: each tensor's update is scaled by a trust ratio formed from
+    whole-tensor L2 norms, so a GPU step is three launches over a device work table
+    (csrc/optim_layerwise.hip): chunk partial sums, one finish per tensor, the update. FLAT runs
+    them over the arena, MULTI over the individual tensors; both build the table with the same
+    partition, so both give the same bits. The table is cached per layout; norms and ratios of
+    the last step stay in a per-optimizer workspace (``trust_ratios``).
+
+    Limits, on purpose: the norms are plain fp32 sums of squares, so a tensor whose sum of
+    squares overflows gets a non-finite ratio and update, as the same formula would in torch --
+    there is no clamp. The update cannot run inside DDP's gradient reduction
+    (``DDP.register_fused_optimizer`` raises TypeError): sharded there, a rank sees 1/W of each
+    tensor and the norms need all of it. Use ``loss.backward(); opt.step()``. ``skip_1d`` and
+    LARS's ``trust_coefficient`` are passed by value: they are fixed once a step is captured."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.dtype != torch.float32:
+                    raise TypeError(f"{type(self).__name__} takes fp32 parameters, got {p.dtype}")
+        self._tables = {}    # layout key -> (work table, workspace)
+        self._last_ws = {}   # group index -> (workspace [3, T], the T parameters in its order)
+        self._flat_gi = {}   # id(arena) -> the group that steps it
+
+    @staticmethod
+    def _skip(g, p) -> bool:
+        return bool(g["skip_1d"]) and p.dim() <= 1
+
+    def trust_ratios(self, gi: int = 0):
+        """``(ws, params)`` of group ``gi``'s last step: ``ws[0]`` = ||p||, ``ws[1]`` = ||u||
+        (LARS: ||g'||), ``ws[2]`` = the trust ratio applied, one column per entry of ``params``.
+        On the GPU this is the kernels' own workspace (reading it synchronises). When a step
+        needed several launches (MULTI with mixed step counts) it is the last one's."""
+        return self._last_ws.get(gi)
+
+    def _table(self, gi, params, ps, gs, s0, s1, skip):
+        key = (tuple(t.data_ptr() for t in ps), tuple(t.data_ptr() for t in gs),
+               tuple(t.data_ptr() for t in s0), tuple(t.data_ptr() for t in s1),
+               tuple(t.numel() for t in ps), tuple(skip))
+        ent = self._tables.get(key)
+        if ent is None:
+            if len(self._tables) >= 8:  # MULTI: gradients move every step
+                self._tables.clear()
+            tab = native().layerwise_table(ps, gs, s0, s1, list(skip))
+            ent = (tab, torch.zeros(3, len(ps), device=ps[0].device, dtype=torch.float32))
+            self._tables[key] = ent
+        self._last_ws[gi] = (ent[1], list(params))
+        return ent
+
+    def _flat_table(self, gi, g, arena, bufs):
+        """The arena's table: rebuilt only when the layout (any base pointer) changes."""
+        key = (id(arena), arena.data.data_ptr(), arena.grad.data_ptr(),
+               tuple(b.data_ptr() for b in bufs), bool(g["skip_1d"]))
+        ent = self._tables.get(key)
+        if ent is None:
+            self._tables.clear()
+            sl = [slice(o, o + n) for o, n in zip(arena.offsets, arena.numels)]
+            tab = native().layerwise_table(
+                [arena.data[s] for s in sl], [arena.grad[s] for s in sl],
+                [bufs[0][s] for s in sl] if len(bufs) > 0 else [],
+                [bufs[1][s] for s in sl] if len(bufs) > 1 else [],
+                [self._skip(g, p) for p in arena.params])
+            ent = (tab, torch.zeros(3, len(sl), device=arena.data.device, dtype=torch.float32))
+            self._tables[key] = ent
+            self._flat_gi[id(arena)] = gi
+            if not hasattr(arena, "_optimizers"):
+                arena._optimizers = weakref.WeakSet()
+            arena._optimizers.add(self)  # a DDP bucket rebuild calls _relayout
+        self._last_ws[gi] = (ent[1], list(arena.params))
+        return ent
+
+    def _relayout(self, arena, remap) -> None:
+        super()._relayout(arena, remap)
+        self._tables.clear()  # the chunk table holds the old arena's addresses
+        gi = self._flat_gi.get(id(arena))
+        if gi is not None:
+            # rebuilt now, eagerly: the next step may be the one a hipGraph records, and
+            # building the table copies from the host
+            bufs = self._flat_bufs.get(id(arena), {})
+            self._flat_table(gi, self.param_groups[gi], arena,
+                             tuple(bufs[k] for k in self._state_keys if k in bufs))
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._tables.clear()
+        self._last_ws = {}
+
+    def _cpu_ws(self, gi, ps):
+        ws = torch.zeros(3, len(ps), dtype=torch.float32)
+        self._last_ws[gi] = (ws, list(ps))
+        return ws
+
+
+class LAMB(_LayerwiseBase):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning", 2019): Adam with a trust
+    ratio per tensor. With ``g' = grad_scale * g`` (negated if ``maximize``)::
+
+        m <- m + (1 - beta1)(g' - m);  v <- beta2 v + (1 - beta2) g'^2
+        u = (m / bc1) / (sqrt(v) / bc2_sqrt + eps) + wd * p
+        r = ||p|| / ||u||  if both norms are positive, else 1
+        p <- p - lr * r * u
+
+    ``skip_1d``: a tensor with ``ndim <= 1`` (biases, norm scales) takes r = 1 and wd = 0; it is
+    a per-tensor flag inside one group, so a whole model stays one flat step. The betas are held
+    as fp32 and the bias corrections formed from those, on every path. State: ``exp_avg``,
+    ``exp_avg_sq``, ``step``. See ``_LayerwiseBase`` for the limits."""
+    _kind = 2
+    _state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.01, *, skip_1d: bool = True, maximize: bool = False,
+                 grad_scale: float = 1.0):
+        if lr < 0 or eps < 0 or weight_decay < 0:
+            raise ValueError("invalid LAMB hyper-parameter")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"invalid betas {betas}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps,
+                                      weight_decay=weight_decay, skip_1d=skip_1d,
+                                      maximize=maximize, grad_scale=grad_scale))
+
+    _scalars = Adam._scalars
+    _bump_step = Adam._bump_step
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, g in enumerate(self.param_groups):
+            ps = [p for p in g["params"] if p.grad is not None]
+            if not ps:
+                continue
+            if not ps[0].is_cuda:
+                self._cpu_step(gi, g, ps)
+                continue
+            C = native()
+            b1, b2 = g["betas"]
+            args = (g["lr"], b1, b2, g["eps"], g["weight_decay"], g["maximize"])
+            arena = _flat_arena(g) if len(ps) == len(g["params"]) else None
+            if arena is not None:
+                key = id(arena)
+                if key not in self._flat_step:
+                    prev = {int(self.state[p]["step"].item()) if torch.is_tensor(
+                        self.state[p].get("step")) else int(self.state[p].get("step") or 0)
+                        for p in arena.params}
+                    if len(prev) == 1:
+                        self._flat_step[key] = prev.pop()
+                if key in self._flat_step:
+                    bufs, _ = self._flat_state(arena, self._state_keys)
+                    tab, ws = self._flat_table(gi, g, arena,
+                                               (bufs["exp_avg"], bufs["exp_avg_sq"]))
+                    # step count and bias corrections advance on the device (graph-safe)
+                    if gi in self._blocks:
+                        blk = self._blocks[gi][0]
+                        self.sync_hyper()
+                    else:
+                        blk = self.hyper_block(gi, step=self._flat_step[key])
+                    self._flat_step[key] += 1
+                    C.opt_step_begin(blk, 2)
+                    C.lamb_layerwise(tab, ws, *args, self._flat_step[key], g["grad_scale"],
+                                     hyper=blk)
+                    continue
+            a2 = arena_of(g["params"])
+            if a2 is not None and id(a2) in self._flat_step:  # leaving the flat path
+                dstep = self.device_step(gi)
+                self._blocks.pop(gi, None)
+                t = torch.tensor(float(dstep if dstep is not None else
+                                       self._flat_step[id(a2)]))
+                self._flat_step.pop(id(a2))
+                for p in a2.params:
+                    self.state[p]["step"] = t.clone()
+            for p in ps:
+                st = self.state[p]
+                for k in self._state_keys:
+                    if st.get(k) is None:
+                        st[k] = torch.zeros_like(p)
+            self._bump_step(ps)
+            by_step = {}
+            for p in ps:
+                by_step.setdefault(int(self.state[p]["step"].item()), []).append(p)
+            for step, lst in by_step.items():
+                st = [self.state[p] for p in lst]
+                tab, ws = self._table(
+                    gi, lst, [_dense(p.data) for p in lst], [_grad_like(p) for p in lst],
+                    [_dense(s["exp_avg"]) for s in st], [_dense(s["exp_avg_sq"]) for s in st],
+                    [self._skip(g, p) for p in lst])
+                C.lamb_layerwise(tab, ws, *args, step, g["grad_scale"])
+        return loss
+
+    def _cpu_step(self, gi, g, ps):
+        """Plain torch code of the formulas; hyper-parameters rounded to fp32 as on the GPU."""
+        lr, eps, wd = _f32(g["lr"]), _f32(g["eps"]), _f32(g["weight_decay"])
+        b1, b2, gs = _f32(g["betas"][0]), _f32(g["betas"][1]), _f32(g["grad_scale"])
+        ws = self._cpu_ws(gi, ps)
+        one = torch.ones((), dtype=torch.float32)
+        for i, p in enumerate(ps):
+            st = self.state[p]
+            if st.get("exp_avg") is None:
+                st["exp_avg"] = torch.zeros_like(p)
+                st["exp_avg_sq"] = torch.zeros_like(p)
+            self._bump_step([p])
+            t = int(st["step"].item())
+            bc1, bc2s = _f32(1 - b1 ** t), _f32((1 - b2 ** t) ** 0.5)
+            grad = p.grad * gs
+            if g["maximize"]:
+                grad = -grad
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            m.add_((grad - m) * (1 - b1))
+            v.mul_(b2).add_(grad.mul(1 - b2).mul_(grad))
+            u = (m / bc1) / (v.sqrt() / bc2s + eps)
+            skip = self._skip(g, p)
+            if wd and not skip:
+                u = u.add(p, alpha=wd)
+            norm_p, norm_u = p.norm(), u.norm()
+            ratio = norm_p / norm_u if (not skip and norm_p > 0 and norm_u > 0) else one
+            ws[0, i], ws[1, i], ws[2, i] = norm_p, norm_u, ratio
+            p.addcmul_(u, ratio * torch.tensor(lr, dtype=torch.float32), value=-1.0)
+
+
+class LARS(_LayerwiseBase):
+    """LARS (You et al., "Large Batch Training of Convolutional Networks", 2017): SGD with a
+    trust ratio per tensor. With ``g' = grad_scale * g`` (negated if ``maximize``)::
+
+        q = trust_coefficient * ||p|| / (||g'|| + wd * ||p|| + eps)  if both norms are positive,
+            else 1
+        d = q * (g' + wd * p)
+
+    then torch-SGD momentum, dampening and nesterov on ``d`` (the buffer is initialised to the
+    first ``d``) and ``p <- p - lr * d``. ``skip_1d`` as for LAMB: q = 1 and wd = 0 for tensors
+    with ``ndim <= 1``. State: ``momentum_buffer``. See ``_LayerwiseBase`` for the limits."""
+    _kind = 1
+    _state_keys = ("momentum_buffer",)
+
+    def __init__(self, params, lr: float, momentum: float = 0.9, dampening: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = False,
+                 trust_coefficient: float = 1e-3, eps: float = 1e-8, *, skip_1d: bool = True,
+                 maximize: bool = False, grad_scale: float = 1.0):
+        if lr < 0 or momentum < 0 or weight_decay < 0 or eps < 0 or trust_coefficient <= 0:
+            raise ValueError("invalid LARS hyper-parameter")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
+                                      weight_decay=weight_decay, nesterov=nesterov,
+                                      trust_coefficient=trust_coefficient, eps=eps,
+                                      skip_1d=skip_1d, maximize=maximize,
+                                      grad_scale=grad_scale))
+
+    def _scalars(self, g) -> tuple:
+        return (float(g["lr"]), float(g["momentum"]), float(g["dampening"]),
+                float(g["weight_decay"]), float(g["eps"]))  # eps takes the kHEps slot
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, g in enumerate(self.param_groups):
+            ps = [p for p in g["params"] if p.grad is not None]
+            if not ps:
+                continue
+            if not ps[0].is_cuda:
+                self._cpu_step(gi, g, ps)
+                continue
+            C = native()
+            mom = g["momentum"] != 0
+            head = (g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"],
+                    g["maximize"])
+            tail = (g["trust_coefficient"], g["eps"], g["grad_scale"])
+            arena = _flat_arena(g) if len(ps) == len(g["params"]) else None
+            if arena is not None:
+                bufs, fresh = (), False
+                if mom:
+                    st, fresh = self._flat_state(arena, self._state_keys)
+                    bufs = (st["momentum_buffer"],)
+                tab, ws = self._flat_table(gi, g, arena, bufs)
+                if gi in self._blocks:
+                    blk = self._blocks[gi][0]
+                    self.sync_hyper()
+                    if fresh:
+                        self._request_first(blk)
+                else:
+                    blk = self.hyper_block(gi, first=fresh)
+                C.opt_step_begin(blk, 1)
+                C.lars_layerwise(tab, ws, *head, False, *tail, hyper=blk)
+                continue
+            new, old = [], []
+            for p in ps:
+                st = self.state[p]
+                if mom and st.get("momentum_buffer") is None:
+                    st["momentum_buffer"] = torch.empty_like(p)
+                    new.append(p)
+                else:
+                    old.append(p)
+            for lst, first in ((new, True), (old, False)):
+                if lst:
+                    tab, ws = self._table(
+                        gi, lst, [_dense(p.data) for p in lst], [_grad_like(p) for p in lst],
+                        [_dense(self.state[p]["momentum_buffer"]) for p in lst] if mom else [],
+                        [], [self._skip(g, p) for p in lst])
+                    C.lars_layerwise(tab, ws, *head, first, *tail)
+        return loss
+
+    def _cpu_step(self, gi, g, ps):
+        """Plain torch code of the formulas; hyper-parameters rounded to fp32 as on the GPU."""
+        lr, mom, damp = _f32(g["lr"]), _f32(g["momentum"]), _f32(g["dampening"])
+        wd0, eps, gs = _f32(g["weight_decay"]), _f32(g["eps"]), _f32(g["grad_scale"])
+        trust = torch.tensor(g["trust_coefficient"], dtype=torch.float32)
+        ws = self._cpu_ws(gi, ps)
+        one = torch.ones((), dtype=torch.float32)
+        for i, p in enumerate(ps):
+            d = p.grad * gs
+            if g["maximize"]:
+                d = -d
+            skip = self._skip(g, p)
+            wd = 0.0 if skip else wd0
+            norm_p, norm_g = p.norm(), d.norm()
+            q = one
+            if not skip and norm_p > 0 and norm_g > 0:
+                q = (trust * norm_p) / (norm_g + wd * norm_p + eps)
+            ws[0, i], ws[1, i], ws[2, i] = norm_p, norm_g, q
+            if wd:
+                d = d.add(p, alpha=wd)
+            d = d * q
+            if mom:
+                st = self.state[p]
+                buf = st.get("momentum_buffer")
+                if buf is None:
+                    buf = d.clone()
+                    st["momentum_buffer"] = buf
+                else:
+                    buf.mul_(mom).add_(d, alpha=1 - damp)
+                d = d.add(buf, alpha=mom) if g["nesterov"] else buf
+            p.add_(d, alpha=-lr)
 
 
 class AdamW(Adam):

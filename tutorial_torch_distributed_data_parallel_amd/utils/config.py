@@ -20,6 +20,9 @@ TRAIN_DEFAULTS = {
     "test_batch_size": 100,      # :95
     "num_epochs": 20,            # :166
     "checkpoint_epoch": 5,       # :167
+    # sgd | adam | adamw | lamb | lars. lamb / lars (large-batch, per-tensor trust ratio) step
+    # after backward: they are never fused into the reduction (fused_optimizer is ignored for
+    # them), and their norms are plain fp32 sums of squares with no clamp on a non-finite norm
     "optimizer": "adam",         # :249
     "lr": 0.001,
     "momentum": 0.9,
