@@ -546,7 +546,34 @@ void check_like(const Tensor& t, const Tensor& p, const char* what) {
 
 // `hyper` (optional device hyper block, kernels.h HyperSlot): the kernel reads lr / momentum /
 // betas / bias corrections / first-step flag / clip coefficient from it (graph-replay safe);
-// the by-value arguments then only carry the structural flags.
+// the by-value arguments then only carry the structural flags. Each struct is filled by position
+// here and nowhere else.
+SgdHyper sgd_hyper(double lr, double momentum, double dampening, double wd, bool nesterov,
+                   bool maximize, bool first_step, double grad_scale,
+                   const c10::optional<Tensor>& hyper) {
+  return SgdHyper{(float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, maximize,
+                  first_step, (float)grad_scale, hyper_ptr(hyper)};
+}
+
+// Bias corrections in double from the betas AS GIVEN: Adam's doubles, LAMB's fp32-rounded ones.
+AdamHyper adam_hyper(double lr, double b1, double b2, double eps, double wd, bool amsgrad,
+                     bool maximize, bool decoupled, int64_t step, double grad_scale,
+                     const c10::optional<Tensor>& hyper) {
+  return AdamHyper{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, amsgrad, maximize,
+                   decoupled, (float)(1.0 - std::pow(b1, (double)step)),
+                   (float)std::sqrt(1.0 - std::pow(b2, (double)step)), (float)grad_scale,
+                   hyper_ptr(hyper)};
+}
+
+// Structural flags only (momentum: whether there is a buffer); every scalar comes from `dev`.
+SgdHyper sgd_flags(bool momentum, bool nesterov, bool maximize, const float* dev) {
+  return SgdHyper{0.f, momentum ? 1.f : 0.f, 0.f, 0.f, nesterov, maximize, false, 1.f, dev};
+}
+
+AdamHyper adam_flags(bool amsgrad, bool maximize, bool decoupled, const float* dev) {
+  return AdamHyper{0.f, 0.f, 0.f, 0.f, 0.f, amsgrad, maximize, decoupled, 1.f, 1.f, 1.f, dev};
+}
+
 void sgd_flat_op(Tensor& p, const Tensor& g, const c10::optional<Tensor>& buf, double lr,
                  double momentum, double dampening, double wd, bool nesterov, bool maximize,
                  bool first_step, double grad_scale, const c10::optional<Tensor>& hyper) {
@@ -556,8 +583,8 @@ void sgd_flat_op(Tensor& p, const Tensor& g, const c10::optional<Tensor>& buf, d
     TORCH_CHECK(buf.has_value() && buf->defined(), "sgd: momentum buffer required");
     check_like(*buf, p, "sgd: momentum buffer");
   }
-  SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, maximize,
-             first_step, (float)grad_scale, hyper_ptr(hyper)};
+  const SgdHyper h = sgd_hyper(lr, momentum, dampening, wd, nesterov, maximize, first_step,
+                               grad_scale, hyper);
   sgd_flat(p.data_ptr<float>(), g.data_ptr<float>(), fptr(buf), p.numel(), h, cur_stream());
 }
 
@@ -573,10 +600,8 @@ void adam_flat_op(Tensor& p, const Tensor& g, Tensor& m, Tensor& v,
     TORCH_CHECK(vmax.has_value() && vmax->defined(), "adam: need vmax");
     check_like(*vmax, p, "adam: vmax");
   }
-  AdamHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, amsgrad, maximize,
-              decoupled, (float)(1.0 - std::pow(b1, (double)step)),
-              (float)std::sqrt(1.0 - std::pow(b2, (double)step)), (float)grad_scale,
-              hyper_ptr(hyper)};
+  const AdamHyper h = adam_hyper(lr, b1, b2, eps, wd, amsgrad, maximize, decoupled, step,
+                                 grad_scale, hyper);
   adam_flat(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
             fptr(vmax), p.numel(), h, cur_stream());
 }
@@ -654,8 +679,8 @@ void sgd_multi_op(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs,
   if (momentum != 0.0) check_list(bufs, ps, "sgd_multi: bufs (momentum != 0)");
   int count = 0;
   auto tab = chunk_table(ps, gs, momentum != 0.0 ? bufs : std::vector<Tensor>{}, {}, {}, &count);
-  SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, maximize,
-             first_step, (float)grad_scale, hyper_ptr(hyper)};
+  const SgdHyper h = sgd_hyper(lr, momentum, dampening, wd, nesterov, maximize, first_step,
+                               grad_scale, hyper);
   sgd_multi(reinterpret_cast<const TensorChunk*>(tab.data_ptr()), count, h, cur_stream());
 }
 
@@ -673,10 +698,8 @@ void adam_multi_op(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs,
   if (amsgrad) check_list(vmaxs, ps, "adam_multi: vmaxs (amsgrad)");
   int count = 0;
   auto tab = chunk_table(ps, gs, ms, vs, amsgrad ? vmaxs : std::vector<Tensor>{}, &count);
-  AdamHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, amsgrad, maximize,
-              decoupled, (float)(1.0 - std::pow(b1, (double)step)),
-              (float)std::sqrt(1.0 - std::pow(b2, (double)step)), (float)grad_scale,
-              hyper_ptr(hyper)};
+  const AdamHyper h = adam_hyper(lr, b1, b2, eps, wd, amsgrad, maximize, decoupled, step,
+                                 grad_scale, hyper);
   adam_multi(reinterpret_cast<const TensorChunk*>(tab.data_ptr()), count, h, cur_stream());
 }
 
@@ -787,10 +810,8 @@ void lamb_layerwise_op(const std::shared_ptr<PyLwTable>& tab, Tensor& ws, double
                        double grad_scale, const c10::optional<Tensor>& hyper, int64_t stages) {
   TORCH_CHECK(tab && tab->has_s0 && tab->has_s1, "lamb: the table needs exp_avg and exp_avg_sq");
   const float fb1 = (float)b1, fb2 = (float)b2;
-  AdamHyper h{(float)lr, fb1, fb2, (float)eps, (float)wd, false, maximize, false,
-              (float)(1.0 - std::pow((double)fb1, (double)step)),
-              (float)std::sqrt(1.0 - std::pow((double)fb2, (double)step)), (float)grad_scale,
-              hyper_ptr(hyper)};
+  const AdamHyper h = adam_hyper(lr, fb1, fb2, eps, wd, false, maximize, false, step,
+                                 grad_scale, hyper);
   lamb_layerwise(lw_view(*tab, ws), h, (int)stages & 7, cur_stream());
 }
 
@@ -800,8 +821,8 @@ void lars_layerwise_op(const std::shared_ptr<PyLwTable>& tab, Tensor& ws, double
                        double grad_scale, const c10::optional<Tensor>& hyper, int64_t stages) {
   TORCH_CHECK(tab, "lars: no table");
   TORCH_CHECK(momentum == 0.0 || tab->has_s0, "lars: momentum needs the table's buffers");
-  SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, maximize,
-             first_step, (float)grad_scale, hyper_ptr(hyper)};
+  const SgdHyper h = sgd_hyper(lr, momentum, dampening, wd, nesterov, maximize, first_step,
+                               grad_scale, hyper);
   lars_layerwise(lw_view(*tab, ws), h, (float)trust, (float)eps, (int)stages & 7, cur_stream());
 }
 
@@ -2038,8 +2059,7 @@ bool gemm_f32_sgd_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig
   wo.kind = 1;
   wo.p = p.data_ptr<float>();
   wo.s0 = mom ? buf->data_ptr<float>() : nullptr;
-  wo.sgd = SgdHyper{0.f, mom ? 1.f : 0.f, 0.f, 0.f, nesterov, maximize, false, 1.f,
-                    block_ptr(hyper)};
+  wo.sgd = sgd_flags(mom, nesterov, maximize, block_ptr(hyper));
   if (a.rowsum != nullptr && bias_p.has_value() && bias_p->defined()) {
     bo.kind = 1;
     bo.p = opt_vec(bias_p, a.M, "gemm_f32_sgd: the bias");
@@ -2082,8 +2102,7 @@ bool gemm_f32_adam_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kconti
     return o;
   };
   OptEpilogue wo = adam_of(p, m, v, vmax, "gemm_f32_adam: state"), bo;
-  wo.adam = AdamHyper{0.f, 0.f, 0.f, 0.f, 0.f, amsgrad, maximize, decoupled, 1.f, 1.f, 1.f,
-                      block_ptr(hyper)};
+  wo.adam = adam_flags(amsgrad, maximize, decoupled, block_ptr(hyper));
   if (a.rowsum != nullptr && bias_p.has_value() && bias_p->defined()) {
     opt_vec(bias_p, a.M, "gemm_f32_adam: the bias");
     bo = adam_of(*bias_p, bias_m, bias_v, bias_vmax, "gemm_f32_adam: bias state");
@@ -2489,8 +2508,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              o.fused.s0 = momentum ? fptr(buf) : nullptr;
              o.fused.s1 = o.fused.s2 = nullptr;
              o.fused.hyper = block_ptr(hyper);
-             o.fused.sgd = SgdHyper{0.f, momentum ? 1.f : 0.f, 0.f, 0.f, nesterov, maximize, false,
-                                    1.f, o.fused.hyper};
+             o.fused.sgd = sgd_flags(momentum, nesterov, maximize, o.fused.hyper);
            })
       .def("set_fused_adam",
            [](RcclOps& o, Tensor p, Tensor m, Tensor v, c10::optional<Tensor> vmax, bool amsgrad,
@@ -2505,8 +2523,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              o.fused.s1 = v.data_ptr<float>();
              o.fused.s2 = amsgrad ? fptr(vmax) : nullptr;
              o.fused.hyper = block_ptr(hyper);
-             o.fused.adam = AdamHyper{0.f, 0.f, 0.f, 0.f, 0.f, amsgrad, maximize, decoupled,
-                                      1.f, 1.f, 1.f, o.fused.hyper};
+             o.fused.adam = adam_flags(amsgrad, maximize, decoupled, o.fused.hyper);
            })
       .def_readwrite("skip_collectives", &RcclOps::skip_collectives)
       .def("clear_fused", [](RcclOps& o) { o.fused = FusedOptimizer{}; })

@@ -2,7 +2,7 @@
 
 The reference steps ``torch.optim.Adam(ddp_model.parameters(), lr=0.001)``
 (REF/multi-GPU-training-torch.py:249, REF/multi-GPU-training-accelerate.py:126); the north star
-adds a fused SGD. Both are ``torch.optim.Optimizer`` subclasses (param_groups, state_dict,
+adds a fused SGD. All are ``torch.optim.Optimizer`` subclasses (param_groups, state_dict,
 load_state_dict, LR schedulers all work) whose ``step`` is:
   * FLAT  -- when the group's parameters are exactly one ParamArena (every DDP model, or any model
              passed through ``flatten_module``) and each .grad is its arena view: ONE kernel over
@@ -16,6 +16,7 @@ bias-corrected Adam with a per-parameter step counter.
 
 LAMB and LARS (torch has neither; their docstrings are the specification) keep the same three
 paths, but a step is three launches: their update is not elementwise (``_LayerwiseBase``).
+``_FusedBase`` owns the host state machine around the kernel calls, shared by all of them.
 """
 from __future__ import annotations
 
@@ -30,8 +31,12 @@ from .._native import native
 from ..parallel.arena import arena_of
 
 
-def _flat_arena(group):
+def _flat_arena(group, ps):
+    """The arena a FLAT step of ``group`` runs over: every parameter has a gradient (``ps``, the
+    ones that do, is all of them), they are exactly one arena, each .grad is its arena view."""
     params = group["params"]
+    if len(ps) != len(params):
+        return None
     a = arena_of(params)
     if a is None:
         return None
@@ -86,7 +91,6 @@ def sync_all_hyper() -> None:
         opt.sync_hyper()
 
 
-
 def _dense(t: torch.Tensor) -> torch.Tensor:
     """A 1-D view of ``t``'s memory in storage order (no copy): the elementwise optimizer kernels
     only need p, grad and state to share one element order. Dense row-major tensors and
@@ -105,9 +109,38 @@ def _grad_like(p: torch.Tensor) -> torch.Tensor:
         return g.contiguous().view(-1)
     return _dense(g.contiguous(memory_format=torch.channels_last))
 
+
+def _closure_loss(closure):
+    with torch.enable_grad():
+        return closure()
+
+
+def _step_of(st) -> int:
+    """A parameter's host step count (a tensor, a plain number, or missing = 0)."""
+    s = st.get("step")
+    return int(s.item()) if torch.is_tensor(s) else int(s or 0)
+
+
+def _adam_scalars(g) -> tuple:
+    b1, b2 = g["betas"]
+    return (float(g["lr"]), float(b1), float(b2), float(g["weight_decay"]), float(g["eps"]))
+
+
+def _momentum_cpu(st, d, momentum, dampening, nesterov):
+    """torch-SGD momentum on the CPU: the buffer starts as the first direction ``d``; returns
+    the direction to apply."""
+    buf = st.get("momentum_buffer")
+    if buf is None:
+        buf = d.clone()
+        st["momentum_buffer"] = buf
+    else:
+        buf.mul_(momentum).add_(d, alpha=1 - dampening)
+    return d.add(buf, alpha=momentum) if nesterov else buf
+
+
 class _FusedBase(Optimizer):
     _state_keys: tuple = ()
-    _kind = 0  # hyper-block kind: 1 SGD, 2 Adam
+    _kind = 0  # hyper-block kind: 1 first-step flag (SGD, LARS), 2 step count too (Adam, LAMB)
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
@@ -175,6 +208,18 @@ class _FusedBase(Optimizer):
     def _request_first(self, blk) -> None:
         blk[hyper_slots()["first_next"]] = 1.0
 
+    def _step_block(self, gi: int, *, device=None, step: int = 0, fresh: bool = False):
+        """Group ``gi``'s block, ready for the step about to be issued: created with step count
+        ``step``, or brought up to date with the host's scalars; ``fresh`` (the momentum buffers
+        were just created) makes that step the one that initialises them."""
+        ent = self._blocks.get(gi)
+        if ent is None:
+            return self.hyper_block(gi, device=device, step=step, first=fresh)
+        self.sync_hyper()
+        if fresh:
+            self._request_first(ent[0])
+        return ent[0]
+
     # ------------------------------------------------------------------ torch API
     def zero_grad(self, set_to_none: bool = True) -> None:
         """torch's zero_grad, without its per-call record_function range / dynamo guard when
@@ -195,9 +240,7 @@ class _FusedBase(Optimizer):
             bufs = {k: arena.new_state() for k in keys}
             self._flat_bufs[id(arena)] = bufs
             fresh = True
-            if not hasattr(arena, "_optimizers"):
-                arena._optimizers = weakref.WeakSet()
-            arena._optimizers.add(self)  # a DDP bucket rebuild re-lays the state out too
+            arena.attach_optimizer(self)  # a DDP bucket rebuild re-lays the state out too
         for i, p in enumerate(arena.params):
             st = self.state[p]
             for k in keys:
@@ -239,29 +282,95 @@ class _FusedBase(Optimizer):
         current hyper-parameters, e.g. after an LR-scheduler step, to the fused update)."""
         return getattr(self, "_fused_ddp", None) is not None
 
+    # ------------------------------------------------------------------ flat step counter
+    # One count for the whole arena, held by the device block (graph replays advance it without
+    # the host) and mirrored in _flat_step; state[p]["step"] is written when somebody looks.
+    def _host_steps(self, arena) -> set:
+        return {_step_of(self.state[p]) for p in arena.params}
+
+    def _enter_flat(self, arena) -> bool:
+        """Whether ``arena`` steps flat: it does already, or its parameters agree on a step
+        count, which becomes the flat one. Mixed counts keep the group on MULTI."""
+        if id(arena) in self._flat_step:
+            return True
+        steps = self._host_steps(arena)
+        if len(steps) != 1:
+            return False
+        self._flat_step[id(arena)] = steps.pop()
+        return True
+
     def _current_flat_step(self, arena) -> int:
         if id(arena) in self._flat_step:
             return self._flat_step[id(arena)]
-        steps = {int(self.state[p]["step"].item()) if torch.is_tensor(self.state[p].get("step"))
-                 else int(self.state[p].get("step") or 0) for p in arena.params}
-        return max(steps) if steps else 0
+        return max(self._host_steps(arena), default=0)
+
+    def _store_flat_step(self, arena) -> None:
+        t = torch.tensor(float(self._flat_step[id(arena)]))
+        for p in arena.params:
+            self.state[p]["step"] = t.clone()
+
+    def _leave_flat(self, gi: int, g) -> None:
+        """Group ``gi`` steps MULTI from here on: if it was flat, its count (the device's, when
+        there is a block) goes back into state[p]["step"] and the block is dropped."""
+        a = arena_of(g["params"])
+        if a is None or id(a) not in self._flat_step:
+            return
+        dstep = self.device_step(gi)
+        self._blocks.pop(gi, None)
+        if dstep is not None:
+            self._flat_step[id(a)] = dstep
+        self._store_flat_step(a)
+        del self._flat_step[id(a)]
 
     def state_dict(self):
-        # materialise the flat step counter (held by the device block: graph replays advance it
-        # without the host) into torch's per-parameter "step" entries
-        if self._kind == 2:
-            for gi, g in enumerate(self.param_groups):
-                a = arena_of(g["params"])
-                dstep = self.device_step(gi)
-                if a is not None and dstep is not None:
-                    self._flat_step[id(a)] = dstep
-        for g in self.param_groups:
+        for gi, g in enumerate(self.param_groups):
             a = arena_of(g["params"])
-            if a is not None and id(a) in self._flat_step:
-                t = torch.tensor(float(self._flat_step[id(a)]))
-                for p in a.params:
-                    self.state[p]["step"] = t.clone()
+            if a is None:
+                continue
+            dstep = self.device_step(gi) if self._kind == 2 else None
+            if dstep is not None:
+                self._flat_step[id(a)] = dstep
+            if id(a) in self._flat_step:
+                self._store_flat_step(a)
         return super().state_dict()
+
+    # ------------------------------------------------------------------ MULTI bookkeeping
+    def _momentum_split(self, ps, mom: bool):
+        """``(parameters, first_step)``: those whose buffer this step creates, and the rest."""
+        new, old = [], []
+        for p in ps:
+            st = self.state[p]
+            if mom and st.get("momentum_buffer") is None:
+                st["momentum_buffer"] = torch.empty_like(p)
+                new.append(p)
+            else:
+                old.append(p)
+        return (new, True), (old, False)
+
+    def _bump_step(self, ps):
+        steps = set()
+        for p in ps:
+            st = self.state[p]
+            s = st.get("step")
+            s = torch.tensor(0.0) if s is None else s
+            s = s + 1 if torch.is_tensor(s) else torch.tensor(float(s) + 1)
+            st["step"] = s
+            steps.add(int(s.item()) if torch.is_tensor(s) else int(s))
+        return steps
+
+    def _by_step(self, ps, keys) -> dict:
+        """Missing state of ``ps`` zero-filled, their step counts advanced: the new count ->
+        the parameters at it (one launch each: the bias corrections go by value)."""
+        for p in ps:
+            st = self.state[p]
+            for k in keys:
+                if st.get(k) is None:
+                    st[k] = torch.zeros_like(p)
+        self._bump_step(ps)
+        by_step = {}
+        for p in ps:
+            by_step.setdefault(_step_of(self.state[p]), []).append(p)
+        return by_step
 
 
 class SGD(_FusedBase):
@@ -284,10 +393,7 @@ class SGD(_FusedBase):
 
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = None if closure is None else _closure_loss(closure)
         if self._fused_step():
             return loss
         tp = getattr(self, "_fused_tp", None)
@@ -300,14 +406,14 @@ class SGD(_FusedBase):
             ps = [p for p in g["params"] if p.grad is not None]
             if not ps:
                 continue
-            hyper = (g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"],
-                     g["maximize"])
             if not ps[0].is_cuda:
                 self._cpu_step(g, ps)
                 continue
             C = native()
+            hyper = (g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"],
+                     g["maximize"])
             mom = g["momentum"] != 0
-            arena = _flat_arena(g) if len(ps) == len(g["params"]) else None
+            arena = _flat_arena(g, ps)
             if arena is not None:
                 buf, fresh = None, False
                 if mom:
@@ -315,31 +421,16 @@ class SGD(_FusedBase):
                     bufs, fresh = self._flat_state(arena, ("momentum_buffer",))
                     buf = bufs["momentum_buffer"]
                 # scalars and the first-step flag come from the device block (graph-safe)
-                if gi in self._blocks:
-                    blk = self._blocks[gi][0]
-                    self.sync_hyper()
-                    if fresh:
-                        self._request_first(blk)
-                else:
-                    blk = self.hyper_block(gi, first=fresh)
+                blk = self._step_block(gi, fresh=fresh)
                 C.opt_step_begin(blk, 1)
-                C.sgd_flat(arena.data, arena.grad, buf, *hyper[:5], hyper[5], False,
-                           g["grad_scale"], hyper=blk)
+                C.sgd_flat(arena.data, arena.grad, buf, *hyper, False, g["grad_scale"],
+                           hyper=blk)
                 continue
-            new, old = [], []
-            for p in ps:
-                st = self.state[p]
-                if mom and st.get("momentum_buffer") is None:
-                    st["momentum_buffer"] = torch.empty_like(p)
-                    new.append(p)
-                else:
-                    old.append(p)
-            for lst, first in ((new, True), (old, False)):
+            for lst, first in self._momentum_split(ps, mom):
                 if lst:
                     bufs = [self.state[p]["momentum_buffer"] for p in lst] if mom else []
                     C.sgd_multi([_dense(p.data) for p in lst], [_grad_like(p) for p in lst],
-                                [_dense(b) for b in bufs], *hyper[:5], hyper[5], first,
-                                g["grad_scale"])
+                                [_dense(b) for b in bufs], *hyper, first, g["grad_scale"])
         return loss
 
     def _cpu_step(self, g, ps):
@@ -350,14 +441,7 @@ class SGD(_FusedBase):
             if g["weight_decay"]:
                 d = d.add(p, alpha=g["weight_decay"])
             if g["momentum"]:
-                st = self.state[p]
-                buf = st.get("momentum_buffer")
-                if buf is None:
-                    buf = d.clone()
-                    st["momentum_buffer"] = buf
-                else:
-                    buf.mul_(g["momentum"]).add_(d, alpha=1 - g["dampening"])
-                d = d.add(buf, alpha=g["momentum"]) if g["nesterov"] else buf
+                d = _momentum_cpu(self.state[p], d, g["momentum"], g["dampening"], g["nesterov"])
             p.add_(d, alpha=-g["lr"])
 
 
@@ -376,87 +460,42 @@ class Adam(_FusedBase):
     _kind = 2
 
     def _scalars(self, g) -> tuple:
-        b1, b2 = g["betas"]
-        return (float(g["lr"]), float(b1), float(b2), float(g["weight_decay"]), float(g["eps"]))
+        return _adam_scalars(g)
 
     def _keys(self, g):
         return ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if g["amsgrad"] else ())
 
-    def _bump_step(self, ps):
-        steps = set()
-        for p in ps:
-            st = self.state[p]
-            s = st.get("step")
-            s = torch.tensor(0.0) if s is None else s
-            s = s + 1 if torch.is_tensor(s) else torch.tensor(float(s) + 1)
-            st["step"] = s
-            steps.add(int(s.item()) if torch.is_tensor(s) else int(s))
-        return steps
-
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = None if closure is None else _closure_loss(closure)
         if self._fused_step():
             return loss
         for gi, g in enumerate(self.param_groups):
             ps = [p for p in g["params"] if p.grad is not None]
             if not ps:
                 continue
-            b1, b2 = g["betas"]
             if not ps[0].is_cuda:
                 self._cpu_step(g, ps)
                 continue
             C = native()
+            b1, b2 = g["betas"]
             keys = self._keys(g)
             args = (g["lr"], b1, b2, g["eps"], g["weight_decay"], g["amsgrad"], g["maximize"],
                     self._decoupled)
-            arena = _flat_arena(g) if len(ps) == len(g["params"]) else None
-            if arena is not None:
-                key = id(arena)
-                if key not in self._flat_step:
-                    prev = {int(self.state[p]["step"].item()) if torch.is_tensor(
-                        self.state[p].get("step")) else int(self.state[p].get("step") or 0)
-                        for p in arena.params}
-                    if len(prev) == 1:
-                        self._flat_step[key] = prev.pop()
-                if key in self._flat_step:
-                    bufs, _ = self._flat_state(arena, keys)
-                    # the step count and bias corrections advance ON THE DEVICE (opt_step_begin),
-                    # so a captured step replays correctly; the host count mirrors it eagerly
-                    if gi in self._blocks:
-                        blk = self._blocks[gi][0]
-                        self.sync_hyper()
-                    else:
-                        blk = self.hyper_block(gi, step=self._flat_step[key])
-                    self._flat_step[key] += 1
-                    C.opt_step_begin(blk, 2)
-                    C.adam_flat(arena.data, arena.grad, bufs["exp_avg"], bufs["exp_avg_sq"],
-                                bufs.get("max_exp_avg_sq"), *args, self._flat_step[key],
-                                g["grad_scale"], hyper=blk)
-                    continue
-            for k2 in list(self._flat_step):  # leaving the flat path: write the counter back
-                a2 = arena_of(g["params"])
-                if a2 is not None and id(a2) == k2:
-                    dstep = self.device_step(gi)
-                    self._blocks.pop(gi, None)
-                    t = torch.tensor(float(dstep if dstep is not None else
-                                           self._flat_step[k2]))
-                    self._flat_step.pop(k2)
-                    for p in a2.params:
-                        self.state[p]["step"] = t.clone()
-            by_step = {}
-            for p in ps:
-                st = self.state[p]
-                for k in keys:
-                    if st.get(k) is None:
-                        st[k] = torch.zeros_like(p)
-            self._bump_step(ps)
-            for p in ps:
-                by_step.setdefault(int(self.state[p]["step"].item()), []).append(p)
-            for step, lst in by_step.items():
+            arena = _flat_arena(g, ps)
+            if arena is not None and self._enter_flat(arena):
+                bufs, _ = self._flat_state(arena, keys)
+                # the step count and bias corrections advance ON THE DEVICE (opt_step_begin),
+                # so a captured step replays correctly; the host count mirrors it eagerly
+                blk = self._step_block(gi, step=self._flat_step[id(arena)])
+                self._flat_step[id(arena)] += 1
+                C.opt_step_begin(blk, 2)
+                C.adam_flat(arena.data, arena.grad, bufs["exp_avg"], bufs["exp_avg_sq"],
+                            bufs.get("max_exp_avg_sq"), *args, self._flat_step[id(arena)],
+                            g["grad_scale"], hyper=blk)
+                continue
+            self._leave_flat(gi, g)
+            for step, lst in self._by_step(ps, keys).items():
                 st = [self.state[p] for p in lst]
                 C.adam_multi([_dense(p.data) for p in lst], [_grad_like(p) for p in lst],
                              [_dense(s["exp_avg"]) for s in st], [_dense(s["exp_avg_sq"]) for s in st],
@@ -567,9 +606,7 @@ class _LayerwiseBase(_FusedBase):
             ent = (tab, torch.zeros(3, len(sl), device=arena.data.device, dtype=torch.float32))
             self._tables[key] = ent
             self._flat_gi[id(arena)] = gi
-            if not hasattr(arena, "_optimizers"):
-                arena._optimizers = weakref.WeakSet()
-            arena._optimizers.add(self)  # a DDP bucket rebuild calls _relayout
+            arena.attach_optimizer(self)  # a DDP bucket rebuild calls _relayout
         self._last_ws[gi] = (ent[1], list(arena.params))
         return ent
 
@@ -622,15 +659,12 @@ class LAMB(_LayerwiseBase):
                                       weight_decay=weight_decay, skip_1d=skip_1d,
                                       maximize=maximize, grad_scale=grad_scale))
 
-    _scalars = Adam._scalars
-    _bump_step = Adam._bump_step
+    def _scalars(self, g) -> tuple:
+        return _adam_scalars(g)
 
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = None if closure is None else _closure_loss(closure)
         for gi, g in enumerate(self.param_groups):
             ps = [p for p in g["params"] if p.grad is not None]
             if not ps:
@@ -641,49 +675,19 @@ class LAMB(_LayerwiseBase):
             C = native()
             b1, b2 = g["betas"]
             args = (g["lr"], b1, b2, g["eps"], g["weight_decay"], g["maximize"])
-            arena = _flat_arena(g) if len(ps) == len(g["params"]) else None
-            if arena is not None:
-                key = id(arena)
-                if key not in self._flat_step:
-                    prev = {int(self.state[p]["step"].item()) if torch.is_tensor(
-                        self.state[p].get("step")) else int(self.state[p].get("step") or 0)
-                        for p in arena.params}
-                    if len(prev) == 1:
-                        self._flat_step[key] = prev.pop()
-                if key in self._flat_step:
-                    bufs, _ = self._flat_state(arena, self._state_keys)
-                    tab, ws = self._flat_table(gi, g, arena,
-                                               (bufs["exp_avg"], bufs["exp_avg_sq"]))
-                    # step count and bias corrections advance on the device (graph-safe)
-                    if gi in self._blocks:
-                        blk = self._blocks[gi][0]
-                        self.sync_hyper()
-                    else:
-                        blk = self.hyper_block(gi, step=self._flat_step[key])
-                    self._flat_step[key] += 1
-                    C.opt_step_begin(blk, 2)
-                    C.lamb_layerwise(tab, ws, *args, self._flat_step[key], g["grad_scale"],
-                                     hyper=blk)
-                    continue
-            a2 = arena_of(g["params"])
-            if a2 is not None and id(a2) in self._flat_step:  # leaving the flat path
-                dstep = self.device_step(gi)
-                self._blocks.pop(gi, None)
-                t = torch.tensor(float(dstep if dstep is not None else
-                                       self._flat_step[id(a2)]))
-                self._flat_step.pop(id(a2))
-                for p in a2.params:
-                    self.state[p]["step"] = t.clone()
-            for p in ps:
-                st = self.state[p]
-                for k in self._state_keys:
-                    if st.get(k) is None:
-                        st[k] = torch.zeros_like(p)
-            self._bump_step(ps)
-            by_step = {}
-            for p in ps:
-                by_step.setdefault(int(self.state[p]["step"].item()), []).append(p)
-            for step, lst in by_step.items():
+            arena = _flat_arena(g, ps)
+            if arena is not None and self._enter_flat(arena):
+                bufs, _ = self._flat_state(arena, self._state_keys)
+                tab, ws = self._flat_table(gi, g, arena, (bufs["exp_avg"], bufs["exp_avg_sq"]))
+                # step count and bias corrections advance on the device (graph-safe)
+                blk = self._step_block(gi, step=self._flat_step[id(arena)])
+                self._flat_step[id(arena)] += 1
+                C.opt_step_begin(blk, 2)
+                C.lamb_layerwise(tab, ws, *args, self._flat_step[id(arena)], g["grad_scale"],
+                                 hyper=blk)
+                continue
+            self._leave_flat(gi, g)
+            for step, lst in self._by_step(ps, self._state_keys).items():
                 st = [self.state[p] for p in lst]
                 tab, ws = self._table(
                     gi, lst, [_dense(p.data) for p in lst], [_grad_like(p) for p in lst],
@@ -756,10 +760,7 @@ class LARS(_LayerwiseBase):
 
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = None if closure is None else _closure_loss(closure)
         for gi, g in enumerate(self.param_groups):
             ps = [p for p in g["params"] if p.grad is not None]
             if not ps:
@@ -772,32 +773,18 @@ class LARS(_LayerwiseBase):
             head = (g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"],
                     g["maximize"])
             tail = (g["trust_coefficient"], g["eps"], g["grad_scale"])
-            arena = _flat_arena(g) if len(ps) == len(g["params"]) else None
+            arena = _flat_arena(g, ps)
             if arena is not None:
                 bufs, fresh = (), False
                 if mom:
                     st, fresh = self._flat_state(arena, self._state_keys)
                     bufs = (st["momentum_buffer"],)
                 tab, ws = self._flat_table(gi, g, arena, bufs)
-                if gi in self._blocks:
-                    blk = self._blocks[gi][0]
-                    self.sync_hyper()
-                    if fresh:
-                        self._request_first(blk)
-                else:
-                    blk = self.hyper_block(gi, first=fresh)
+                blk = self._step_block(gi, fresh=fresh)
                 C.opt_step_begin(blk, 1)
                 C.lars_layerwise(tab, ws, *head, False, *tail, hyper=blk)
                 continue
-            new, old = [], []
-            for p in ps:
-                st = self.state[p]
-                if mom and st.get("momentum_buffer") is None:
-                    st["momentum_buffer"] = torch.empty_like(p)
-                    new.append(p)
-                else:
-                    old.append(p)
-            for lst, first in ((new, True), (old, False)):
+            for lst, first in self._momentum_split(ps, mom):
                 if lst:
                     tab, ws = self._table(
                         gi, lst, [_dense(p.data) for p in lst], [_grad_like(p) for p in lst],
@@ -828,14 +815,7 @@ class LARS(_LayerwiseBase):
                 d = d.add(p, alpha=wd)
             d = d * q
             if mom:
-                st = self.state[p]
-                buf = st.get("momentum_buffer")
-                if buf is None:
-                    buf = d.clone()
-                    st["momentum_buffer"] = buf
-                else:
-                    buf.mul_(mom).add_(d, alpha=1 - damp)
-                d = d.add(buf, alpha=mom) if g["nesterov"] else buf
+                d = _momentum_cpu(self.state[p], d, mom, damp, g["nesterov"])
             p.add_(d, alpha=-lr)
 
 

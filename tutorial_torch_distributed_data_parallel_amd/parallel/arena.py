@@ -14,6 +14,8 @@ vectorised kernels; the gaps stay zero in both arenas.
 """
 from __future__ import annotations
 
+import weakref
+
 import torch
 
 ALIGN = 64
@@ -63,6 +65,7 @@ class ParamArena:
         self.device, self.dtype = device, dtype
         self.data = torch.zeros(self.numel, device=device, dtype=dtype)
         self.grad = torch.zeros(self.numel, device=device, dtype=dtype)
+        self.optimizers = weakref.WeakSet()  # see attach_optimizer
         with torch.no_grad():
             for p, o, n in zip(uniq, self.offsets, self.numels):
                 view = slot_view(self.data, p, o)
@@ -92,6 +95,12 @@ class ParamArena:
     def new_state(self) -> torch.Tensor:
         """A zeroed buffer with the arena's layout (optimizer state: momentum, exp_avg, ...)."""
         return torch.zeros_like(self.data)
+
+    def attach_optimizer(self, opt) -> None:
+        """``opt`` keeps arena-shaped state or tables of arena addresses: whoever calls
+        ``relayout`` hands its ``remap`` to ``opt._relayout`` of every one in ``optimizers``
+        (held weakly)."""
+        self.optimizers.add(opt)
 
     def relayout(self, order):
         """Re-lay the arena out with the parameters in ``order`` (indices into ``self.params``):

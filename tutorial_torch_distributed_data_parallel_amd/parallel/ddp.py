@@ -268,7 +268,7 @@ class DistributedDataParallel(nn.Module):
         self._factor = {new_of[i]: (o, n, None if bi is None else new_of[bi])
                         for i, (o, n, bi) in self._factor.items()}
         remap = self.arena.relayout(order)
-        for opt in list(getattr(self.arena, "_optimizers", ())):
+        for opt in list(self.arena.optimizers):
             opt._relayout(self.arena, remap)
         self._bounds = self._plan_buckets()
         self._build_reducer()

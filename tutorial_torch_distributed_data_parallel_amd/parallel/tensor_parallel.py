@@ -597,13 +597,7 @@ class TensorParallelMLP(nn.Module):
         if g["momentum"] != 0:
             bufs, fresh = opt._flat_state(a, ("momentum_buffer",))
             buf = bufs["momentum_buffer"]
-        if 0 in opt._blocks:
-            blk = opt._blocks[0][0]
-            opt.sync_hyper()
-            if fresh:
-                opt._request_first(blk)
-        else:
-            blk = opt.hyper_block(0, device=self.fc1.weight.device, first=fresh)
+        blk = opt._step_block(0, device=self.fc1.weight.device, fresh=fresh)
         native().opt_step_begin(blk, 1)
         self._fstate = (buf, blk, g)
         self._done = {}
