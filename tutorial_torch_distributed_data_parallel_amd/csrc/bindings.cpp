@@ -110,26 +110,70 @@ void gemm_f32_launch(const GemmF32Args& a, const GemmPlan& plan, const Tensor& C
   gemm_f32_run(a, plan, plan.ws_floats > 0 ? ws.data_ptr<float>() : nullptr, s);
 }
 
+// What a gemm_f32 call runs: the operands and optional tensors as GemmF32Args (the scalars beta,
+// rowsum_beta and relu, which no plan depends on, are left to the caller), the plan, and whether
+// the gate is applied by a gate_inplace pass after the kernel. Shared by gemm_f32_op and
+// gemm_f32_plan_for_op, so a test reads the plan of exactly the call it is about to make.
+struct GemmF32Call {
+  GemmF32Args a;
+  GemmPlan plan;
+  const float* gate_after = nullptr;  // != null: the gate (leading dimension a.ldgate) runs after
+};
+GemmF32Call gemm_f32_call(const Tensor& A, const Tensor& B, const Tensor& C, bool a_kcontig,
+                          bool b_kcontig, const c10::optional<Tensor>& mask,
+                          const c10::optional<Tensor>& bias, const c10::optional<Tensor>& rowsum,
+                          const c10::optional<Tensor>& gate) {
+  GemmF32Call c;
+  GemmF32Args& a = c.a;
+  a = gemm_f32_args(A, B, C, a_kcontig, b_kcontig, false);
+  a.mask = opt_mat(mask, A.size(0), A.size(1), &a.ldmask, "gemm: mask (A's shape)");
+  a.bias = opt_vec(bias, a.N, "gemm: bias");
+  a.rowsum = opt_vec(rowsum, a.M, "gemm: rowsum");
+  a.gate = opt_mat(gate, a.M, a.N, &a.ldgate, "gemm: gate (C's shape)");
+  // the fast kernel's row-vector epilogue reads the gate as 16-B rows
+  const bool misaligned = a.gate && (((uintptr_t)a.gate & 15) != 0 || a.ldgate % 4 != 0);
+  c.plan = gemm_f32_plan(a, num_cus(C.get_device()));
+  if (misaligned && c.plan.fast) {
+    c.gate_after = a.gate;
+    a.gate = nullptr;
+  }
+  return c;
+}
+
 void gemm_f32_op(const Tensor& A, const Tensor& B, Tensor& C, bool a_kcontig, bool b_kcontig,
                  const c10::optional<Tensor>& mask, const c10::optional<Tensor>& bias,
                  const c10::optional<Tensor>& rowsum, double beta, double rowsum_beta,
                  bool relu, const c10::optional<Tensor>& gate) {
-  GemmF32Args a = gemm_f32_args(A, B, C, a_kcontig, b_kcontig, false);
-  a.mask = opt_mat(mask, A.size(0), A.size(1), &a.ldmask, "gemm: mask (A's shape)");
-  a.bias = opt_vec(bias, a.N, "gemm: bias");
-  a.rowsum = opt_vec(rowsum, a.M, "gemm: rowsum");
+  GemmF32Call c = gemm_f32_call(A, B, C, a_kcontig, b_kcontig, mask, bias, rowsum, gate);
+  GemmF32Args& a = c.a;
   a.beta = (float)beta;
   a.rowsum_beta = (float)rowsum_beta;
   a.relu = relu;
-  a.gate = opt_mat(gate, a.M, a.N, &a.ldgate, "gemm: gate (C's shape)");
-  // the fast kernel's row-vector epilogue reads the gate as 16-B rows
-  bool gate_after = a.gate && (((uintptr_t)a.gate & 15) != 0 || a.ldgate % 4 != 0);
-  GemmPlan plan = gemm_f32_plan(a, num_cus(C.get_device()));
-  const float* g = a.gate;
-  if (gate_after && plan.fast) a.gate = nullptr;
-  else gate_after = false;
-  gemm_f32_launch(a, plan, C, cur_stream());
-  if (gate_after) gate_inplace(a.C, a.ldc, g, gate->stride(0), a.M, a.N, cur_stream());
+  gemm_f32_launch(a, c.plan, C, cur_stream());
+  if (c.gate_after) gate_inplace(a.C, a.ldc, c.gate_after, a.ldgate, a.M, a.N, cur_stream());
+}
+
+// The plan gemm_f32 would run for these very tensors (layouts, strides and alignment included)
+// under the current knobs; launches nothing.
+py::dict gemm_f32_plan_for_op(const Tensor& A, const Tensor& B, const Tensor& C, bool a_kcontig,
+                              bool b_kcontig, const c10::optional<Tensor>& mask,
+                              const c10::optional<Tensor>& bias,
+                              const c10::optional<Tensor>& rowsum,
+                              const c10::optional<Tensor>& gate) {
+  const GemmF32Call c = gemm_f32_call(A, B, C, a_kcontig, b_kcontig, mask, bias, rowsum, gate);
+  const GemmPlan& p = c.plan;
+  py::dict d;
+  d["skinny"] = p.skinny;
+  d["emu8"] = p.emu8;
+  d["fast"] = p.fast;
+  d["tile"] = p.tile;
+  d["bm"] = p.bm;
+  d["bn"] = p.bn;
+  d["stages"] = p.stages;
+  d["splits"] = p.splits;
+  d["k_per_split"] = p.k_per_split;
+  d["gate_after"] = c.gate_after != nullptr;
+  return d;
 }
 
 // Mixed-precision GEMM (gemm_bf16.hip): fp32 tensors, operands rounded once to bf16, fp32
@@ -2150,6 +2194,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias_m") = py::none(), py::arg("bias_v") = py::none(),
         py::arg("bias_vmax") = py::none());
   m.def("gemm_f32_plan", &gemm_f32_plan_op);
+  m.def("gemm_f32_plan_for", &gemm_f32_plan_for_op, py::arg("A"), py::arg("B"), py::arg("C"),
+        py::arg("a_kcontig"), py::arg("b_kcontig"), py::arg("mask") = py::none(),
+        py::arg("bias") = py::none(), py::arg("rowsum") = py::none(),
+        py::arg("gate") = py::none());
   m.def("gemm_planes", &gemm_planes_op, py::arg("Ap"), py::arg("B"), py::arg("C"),
         py::arg("b_kcontig"), py::arg("bias") = py::none(), py::arg("relu") = false,
         py::arg("gate") = py::none(), py::arg("out_planes") = py::none());

@@ -1511,6 +1511,9 @@ void gemm_f32_fast_plan(const GemmF32Args& a, int num_cus, GemmPlan& plan) {
   const int nk = ceil_div(kps, kBK);
   plan.stages = (fn == 1 && nk > 4) ? 3 : 2;
   if (o_stages == 2 || o_stages == 3) plan.stages = o_stages;
+  // fewer K steps than stages: the prologue's extra stage would only DMA a clamped (valid, but
+  // not zero-filled) source tile that no wave reads; a forced third stage falls back to two
+  if (nk < 3) plan.stages = 2;
 }
 
 static FastParams fast_params(const GemmF32Args& a, const GemmPlan& plan, float* ws) {
