@@ -963,6 +963,14 @@ Tensor bn_merge_op(const Tensor& gathered, int64_t C, double eps, double momentu
   return stats;
 }
 
+// The fused activation of the BatchNorm forwards: 0 none, 1 ReLU, 2 ReLU6 (a Python bool still
+// converts: False / True are 0 / 1).
+static int bn_act_kind(int64_t relu) {
+  TORCH_CHECK(relu >= 0 && relu <= 2, "batch norm: activation must be 0 (none), 1 (ReLU) or 2 ",
+              "(ReLU6), got ", relu);
+  return (int)relu;
+}
+
 // the ReLU mask of the [rows, C % 4 == 0] form: uint8, one byte per 4 channels
 static const uint8_t* mask_ptr(const c10::optional<Tensor>& m, const Tensor& x) {
   if (!m.has_value() || !m->defined()) return nullptr;
@@ -983,7 +991,7 @@ static uint16_t* planes_ptr(const c10::optional<Tensor>& p, const Tensor& x) {
 }
 
 Tensor bn_elemt_op(const Tensor& x, const Tensor& stats, const c10::optional<Tensor>& w,
-                   const c10::optional<Tensor>& b, bool relu,
+                   const c10::optional<Tensor>& b, int64_t relu,
                    const c10::optional<Tensor>& residual,
                    const c10::optional<Tensor>& mask_out,
                    const c10::optional<Tensor>& planes_out) {
@@ -997,7 +1005,7 @@ Tensor bn_elemt_op(const Tensor& x, const Tensor& stats, const c10::optional<Ten
   }
   auto y = at::empty_like(x);
   const float* sp = stats.data_ptr<float>();
-  bn_elemt(x.data_ptr<float>(), sp, sp + C, fptr(w), fptr(b), N, C, HW, relu,
+  bn_elemt(x.data_ptr<float>(), sp, sp + C, fptr(w), fptr(b), N, C, HW, bn_act_kind(relu),
            y.data_ptr<float>(), cur_stream(), fptr(residual),
            const_cast<uint8_t*>(mask_ptr(mask_out, x)), planes_ptr(planes_out, x));
   return y;
@@ -1006,7 +1014,7 @@ Tensor bn_elemt_op(const Tensor& x, const Tensor& stats, const c10::optional<Ten
 // one rank: (y, stats) from this rank's moments [mean | var | count] -- bn_merge fused in
 std::vector<Tensor> bn_elemt_local_op(const Tensor& x, const Tensor& moments,
                                       const c10::optional<Tensor>& w,
-                                      const c10::optional<Tensor>& b, bool relu, double eps,
+                                      const c10::optional<Tensor>& b, int64_t relu, double eps,
                                       double momentum, const c10::optional<Tensor>& rmean,
                                       const c10::optional<Tensor>& rvar,
                                       const c10::optional<Tensor>& num_batches,
@@ -1030,7 +1038,7 @@ std::vector<Tensor> bn_elemt_local_op(const Tensor& x, const Tensor& moments,
   auto y = at::empty_like(x);
   auto stats = at::empty({2 * C + 1}, x.options());
   const bool ok = bn_elemt_local(x.data_ptr<float>(), moments.data_ptr<float>(), fptr(w),
-                                 fptr(b), N, C, relu, (float)eps, (float)momentum,
+                                 fptr(b), N, C, bn_act_kind(relu), (float)eps, (float)momentum,
                                  stats.data_ptr<float>(), fptr(rmean), fptr(rvar), nb,
                                  y.data_ptr<float>(), const_cast<uint8_t*>(mask_ptr(mask_out, x)),
                                  planes_ptr(planes_out, x), cur_stream(), fptr(residual));
@@ -1041,7 +1049,7 @@ std::vector<Tensor> bn_elemt_local_op(const Tensor& x, const Tensor& moments,
 // one rank, a batch of rows: (y, stats) with the statistics computed in the same launch
 // (bn1d_local_fwd); [] when the shape is not taken (the caller runs bn_moments + bn_elemt_local)
 std::vector<Tensor> bn1d_local_fwd_op(const Tensor& x, const c10::optional<Tensor>& w,
-                                      const c10::optional<Tensor>& b, bool relu, double eps,
+                                      const c10::optional<Tensor>& b, int64_t relu, double eps,
                                       double momentum, const c10::optional<Tensor>& rmean,
                                       const c10::optional<Tensor>& rvar,
                                       const c10::optional<Tensor>& num_batches,
@@ -1061,8 +1069,9 @@ std::vector<Tensor> bn1d_local_fwd_op(const Tensor& x, const c10::optional<Tenso
       TORCH_CHECK((*t)->numel() == C && (*t)->is_contiguous(), "bn1d_local_fwd: [C] parameters");
   auto y = at::empty_like(x);
   auto stats = at::empty({2 * C + 1}, x.options());
-  const bool ok = bn1d_local_fwd(x.data_ptr<float>(), fptr(w), fptr(b), N, C, relu, (float)eps,
-                                 (float)momentum, stats.data_ptr<float>(), fptr(rmean),
+  const bool ok = bn1d_local_fwd(x.data_ptr<float>(), fptr(w), fptr(b), N, C,
+                                 bn_act_kind(relu), (float)eps, (float)momentum,
+                                 stats.data_ptr<float>(), fptr(rmean),
                                  fptr(rvar), nb, y.data_ptr<float>(),
                                  const_cast<uint8_t*>(mask_ptr(mask_out, x)),
                                  planes_ptr(planes_out, x), cur_stream());
@@ -1082,7 +1091,7 @@ Tensor bn1d_moments_op(const Tensor& x) {
 
 std::vector<Tensor> bn1d_gathered_fwd_op(const Tensor& x, const Tensor& gathered,
                                          const c10::optional<Tensor>& w,
-                                         const c10::optional<Tensor>& b, bool relu, double eps,
+                                         const c10::optional<Tensor>& b, int64_t relu, double eps,
                                          double momentum, const c10::optional<Tensor>& rmean,
                                          const c10::optional<Tensor>& rvar,
                                          const c10::optional<Tensor>& num_batches,
@@ -1107,7 +1116,7 @@ std::vector<Tensor> bn1d_gathered_fwd_op(const Tensor& x, const Tensor& gathered
   auto y = at::empty_like(x);
   auto stats = at::empty({2 * C + 1}, x.options());
   const bool ok = bn1d_gathered_fwd(x.data_ptr<float>(), gathered.data_ptr<float>(), R, fptr(w),
-                                    fptr(b), N, C, relu, (float)eps, (float)momentum,
+                                    fptr(b), N, C, bn_act_kind(relu), (float)eps, (float)momentum,
                                     stats.data_ptr<float>(), fptr(rmean), fptr(rvar), nb,
                                     y.data_ptr<float>(),
                                     const_cast<uint8_t*>(mask_ptr(mask_out, x)),
@@ -1179,13 +1188,13 @@ Tensor bn1d_local_bwd_op(const Tensor& dy, const Tensor& x, const Tensor& stats,
 
 Tensor bn_eval_op(const Tensor& x, const Tensor& rmean, const Tensor& rvar,
                   const c10::optional<Tensor>& w, const c10::optional<Tensor>& b, double eps,
-                  bool relu) {
+                  int64_t relu) {
   CHECK_GPU(x); CHECK_F32(x); CHECK_CONTIG(x);
   int N, C, HW;
   bn_dims(x, N, C, HW);
   auto y = at::empty_like(x);
   bn_eval(x.data_ptr<float>(), rmean.data_ptr<float>(), rvar.data_ptr<float>(), fptr(w), fptr(b),
-          N, C, HW, (float)eps, relu, y.data_ptr<float>(), cur_stream());
+          N, C, HW, (float)eps, bn_act_kind(relu), y.data_ptr<float>(), cur_stream());
   return y;
 }
 
@@ -1193,7 +1202,7 @@ Tensor bn_eval_op(const Tensor& x, const Tensor& rmean, const Tensor& rvar,
 Tensor bn_bwd_reduce_op(const Tensor& dy, const Tensor& x, const Tensor& stats,
                         const c10::optional<Tensor>& y_relu, const c10::optional<Tensor>& dw,
                         const c10::optional<Tensor>& db, double grad_beta,
-                        const c10::optional<Tensor>& mask) {
+                        const c10::optional<Tensor>& mask, int64_t act) {
   CHECK_GPU(dy); CHECK_F32(dy); CHECK_CONTIG(dy); CHECK_CONTIG(x);
   int N, C, HW;
   bn_dims(x, N, C, HW);
@@ -1203,7 +1212,7 @@ Tensor bn_bwd_reduce_op(const Tensor& dy, const Tensor& x, const Tensor& stats,
   const float* sp = stats.data_ptr<float>();
   bn_bwd_reduce(dy.data_ptr<float>(), x.data_ptr<float>(), sp, sp + C, fptr(y_relu), N, C, HW,
                 splits, ws.data_ptr<float>(), sums.data_ptr<float>(), fptr(dw), fptr(db),
-                (float)grad_beta, cur_stream(), mask_ptr(mask, x));
+                (float)grad_beta, cur_stream(), mask_ptr(mask, x), bn_act_kind(act));
   return sums;
 }
 
@@ -1212,7 +1221,7 @@ std::vector<Tensor> bn_bwd_elemt_op(const Tensor& dy, const Tensor& x, const Ten
                                     const c10::optional<Tensor>& w, const Tensor& sums,
                                     const c10::optional<Tensor>& y_relu, bool residual_grad,
                                     const c10::optional<Tensor>& mask,
-                                    const c10::optional<Tensor>& planes_out) {
+                                    const c10::optional<Tensor>& planes_out, int64_t act) {
   CHECK_GPU(dy); CHECK_F32(dy); CHECK_CONTIG(dy); CHECK_CONTIG(x);
   int N, C, HW;
   bn_dims(x, N, C, HW);
@@ -1223,7 +1232,7 @@ std::vector<Tensor> bn_bwd_elemt_op(const Tensor& dy, const Tensor& x, const Ten
   bn_bwd_elemt(dy.data_ptr<float>(), x.data_ptr<float>(), sp, sp + C, fptr(w),
                sums.data_ptr<float>(), fptr(y_relu), sp + 2 * C, N, C, HW, dx.data_ptr<float>(),
                cur_stream(), residual_grad ? dres.data_ptr<float>() : nullptr,
-               mask_ptr(mask, x), planes_ptr(planes_out, x));
+               mask_ptr(mask, x), planes_ptr(planes_out, x), bn_act_kind(act));
   if (residual_grad) return {dx, dres};
   return {dx};
 }
@@ -1529,6 +1538,28 @@ Tensor conv_grouped_fwd_op(const Tensor& x, const Tensor& w, const c10::optional
   return y;
 }
 
+// depthwise forward that also emits the output's BatchNorm statistics: (y, part [T, 3, Cout]),
+// or (y) alone when the geometry has no statistics form (conv_dw_stats_tiles == 0)
+std::vector<Tensor> conv_dw_fwd_stats_op(const Tensor& x, const Tensor& w, int64_t sh, int64_t sw,
+                                         int64_t ph, int64_t pw, int64_t groups) {
+  CHECK_GPU(x); CHECK_F32(x); CHECK_CL(x);
+  const GroupConvGeom g = group_geom(x.sizes().vec(), w, sh, sw, ph, pw, groups);
+  check_aligned16(x, "conv (grouped): x"); check_aligned16(w, "conv (grouped): weight");
+  auto y = at::empty({g.N, g.Cout, (g.H + 2 * g.ph - g.R) / g.sh + 1,
+                      (g.W + 2 * g.pw - g.S) / g.sw + 1},
+                     x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const int T = conv_dw_stats_tiles(g);
+  if (T == 0) {
+    conv_grouped_fwd(g, x.data_ptr<float>(), w.data_ptr<float>(), nullptr, false,
+                     y.data_ptr<float>(), cur_stream());
+    return {y};
+  }
+  auto part = at::empty({T, 3, g.Cout}, x.options().memory_format(at::MemoryFormat::Contiguous));
+  conv_grouped_fwd(g, x.data_ptr<float>(), w.data_ptr<float>(), nullptr, false,
+                   y.data_ptr<float>(), cur_stream(), part.data_ptr<float>());
+  return {y, part};
+}
+
 // with `out`: written there, out = dgrad (+ out when accumulate)
 Tensor conv_grouped_dgrad_op(const Tensor& dy, const Tensor& w, std::vector<int64_t> x_shape,
                              int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t groups,
@@ -1712,6 +1743,29 @@ Tensor relu_mask_op(const Tensor& dy, const Tensor& y) {
   relu_mask(dy.data_ptr<float>(), y.data_ptr<float>(), dy.numel(), g.data_ptr<float>(),
             cur_stream());
   return g;
+}
+
+// Stand-alone ReLU6 over any dense layout: (y, gate) with the gate one bit per element in memory
+// order; its backward reads dy in the same layout and the gate
+std::vector<Tensor> relu6_fwd_op(const Tensor& x) {
+  CHECK_GPU(x); CHECK_F32(x);
+  TORCH_CHECK(x.is_non_overlapping_and_dense(), "relu6: a dense tensor expected");
+  auto y = at::empty_like(x);
+  auto gate = at::empty({(x.numel() + 7) / 8}, x.options().dtype(at::kByte));
+  relu6_fwd(x.data_ptr<float>(), x.numel(), y.data_ptr<float>(), gate.data_ptr<uint8_t>(),
+            cur_stream());
+  return {y, gate};
+}
+
+Tensor relu6_bwd_op(const Tensor& dy, const Tensor& gate) {
+  CHECK_GPU(dy); CHECK_F32(dy); CHECK_GPU(gate); CHECK_CONTIG(gate);
+  TORCH_CHECK(dy.is_non_overlapping_and_dense(), "relu6_bwd: a dense tensor expected");
+  TORCH_CHECK(gate.scalar_type() == at::kByte && gate.numel() == (dy.numel() + 7) / 8,
+              "relu6_bwd: gate must be ceil(numel / 8) uint8 bytes");
+  auto dx = at::empty_like(dy);
+  relu6_bwd(dy.data_ptr<float>(), gate.data_ptr<uint8_t>(), dy.numel(), dx.data_ptr<float>(),
+            cur_stream());
+  return dx;
 }
 
 // x [n, ...] fp32 contiguous, y [n] int64, idx [B] int64 (all on the GPU) -> (x[idx], y[idx])
@@ -2315,6 +2369,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_grouped_fwd", &conv_grouped_fwd_op, py::arg("x"), py::arg("w"), py::arg("bias"),
         py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("groups"),
         py::arg("relu") = false);
+  m.def("conv_dw_fwd_stats", &conv_dw_fwd_stats_op, py::arg("x"), py::arg("w"), py::arg("sh"),
+        py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("groups"));
   m.def("conv_grouped_dgrad", &conv_grouped_dgrad_op, py::arg("dy"), py::arg("w"),
         py::arg("x_shape"), py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"),
         py::arg("groups"), py::arg("out") = py::none(), py::arg("accumulate") = false);
@@ -2357,6 +2413,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout", &dropout_op);
   m.def("add_relu", &add_relu_op);
   m.def("relu_mask", &relu_mask_op);
+  m.def("relu6_fwd", &relu6_fwd_op, py::arg("x"));
+  m.def("relu6_bwd", &relu6_bwd_op, py::arg("dy"), py::arg("gate"));
   // this rank's factors of a factored Linear weight into slot `rank` of the all-gather buffers:
   // g [B][out] * alpha and x [B][in]; each slot holds `slot_rows` >= B rows (the batch size the
   // ranks agreed on) and rows B.. are zeroed, so a smaller (ragged last) batch on some rank
@@ -2439,10 +2497,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_eval", &bn_eval_op);
   m.def("bn_bwd_reduce", &bn_bwd_reduce_op, py::arg("dy"), py::arg("x"), py::arg("stats"),
         py::arg("y_relu"), py::arg("dw"), py::arg("db"), py::arg("grad_beta"),
-        py::arg("mask") = py::none());
+        py::arg("mask") = py::none(), py::arg("act") = 1);
   m.def("bn_bwd_elemt", &bn_bwd_elemt_op, py::arg("dy"), py::arg("x"), py::arg("stats"),
         py::arg("w"), py::arg("sums"), py::arg("y_relu"), py::arg("residual_grad") = false,
-        py::arg("mask") = py::none(), py::arg("planes_out") = py::none());
+        py::arg("mask") = py::none(), py::arg("planes_out") = py::none(), py::arg("act") = 1);
 
   m.def("rccl_unique_id", &unique_id_op);
   m.def("debug_spin_ms", [](int ms) { debug_spin_ms(ms, cur_stream()); });

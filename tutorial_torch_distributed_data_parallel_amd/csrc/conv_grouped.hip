@@ -24,11 +24,15 @@
 //                         held in registers (3x3 and 5x5 with m == 1); any other filter size or a
 //                         channel multiplier m > 1 takes the <.., 0, 0> form, which reads taps
 //                         and the m-strided channels from memory.
+//                         dwconv_kernel<false, R, S, true> (register-tap forward) also emits the
+//                         output's BatchNorm statistics: one (count, mean, M2) partial per
+//                         (block, channel), reduced in LDS in a fixed order.
 //   dwconv_wgrad_kernel   a thread owns one tap of 4 output channels over a pixel range.
 // No pass uses atomics: every result is bitwise reproducible.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <stdexcept>
 
 #include "kernels.h"
 
@@ -236,18 +240,28 @@ struct DwArgs {
 };
 constexpr int kDwPix = 8;  // consecutive output pixels per thread (the taps are loaded once)
 
-template <bool DGRAD, int R_, int S_>
+// STATS (forward, register taps, no bias / ReLU): the block also writes the BatchNorm statistics
+// of the outputs it produced, part[blockIdx.x][3][OC] = (count, mean, M2) per channel -- the
+// [T][3][C] partials bn_moments_partials merges (norm.hip moments_partials_l1). A thread sums its
+// <= 8 pixels shifted by its first pixel's value (s1 = sum (v - K), s2 = sum (v - K)^2: mean =
+// K + s1 / n, M2 = s2 - s1^2 / n, the shifted-sum form of the GEMM epilogue's statistics); the
+// block's threads of one channel quad are then Chan-merged through LDS in ascending thread
+// order. No atomics, and the partition depends on the geometry alone: bitwise reproducible. A
+// channel no thread of the block covers gets count 0.
+template <bool DGRAD, int R_, int S_, bool STATS = false>
 __global__ __launch_bounds__(256) void dwconv_kernel(DwArgs a, const float* __restrict__ in,
                                                      const float* __restrict__ w,
                                                      const float* __restrict__ bias,
                                                      float* __restrict__ out, int relu,
-                                                     int accumulate) {
+                                                     int accumulate,
+                                                     float* __restrict__ part = nullptr) {
+  static_assert(!STATS || (!DGRAD && R_ > 0), "statistics: register-tap forward only");
   const int OQ = a.OC / 4;
   const long Mout = (long)a.N * a.OH * a.OW;
   const long item = (long)blockIdx.x * 256 + threadIdx.x;
   const int oq = (int)(item % OQ);
   const long mb = (item / OQ) * kDwPix;
-  if (mb >= Mout) return;
+  if (!STATS && mb >= Mout) return;  // (with STATS every thread reaches the block reduction)
   const int RS = a.R * a.S;
   f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
   if (bias != nullptr) bv = *reinterpret_cast<const f32x4*>(bias + 4 * oq);
@@ -263,6 +277,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DwArgs a, const float* __re
   }
 
   const long me = min(Mout, mb + kDwPix);
+  f32x4 sk = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = sk, s2 = sk;  // STATS: shift, shifted sums
   for (long m = mb; m < me; ++m) {
     const int ow = (int)(m % a.OW), oh = (int)((m / a.OW) % a.OH);
     const int n = (int)(m / ((long)a.OW * a.OH));
@@ -315,6 +330,51 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DwArgs a, const float* __re
       for (int j = 0; j < 4; ++j) o[j] = o[j] > 0.f ? o[j] : 0.f;
     }
     *dst = o;
+    if constexpr (STATS) {
+      if (m == mb) sk = o;
+      const f32x4 d = o - sk;
+      s1 += d;
+      s2 += d * d;
+    }
+  }
+  if constexpr (STATS) {
+    __shared__ float sn[256];
+    __shared__ float sm[2][4][256];  // mean | M2, per channel of the quad, per thread
+    const float n = me > mb ? (float)(me - mb) : 0.f;
+    sn[threadIdx.x] = n;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float mu = n > 0.f ? s1[j] / n : 0.f;
+      const float m2 = n > 0.f ? s2[j] - s1[j] * mu : 0.f;
+      sm[0][j][threadIdx.x] = sk[j] + mu;
+      sm[1][j][threadIdx.x] = m2 > 0.f ? m2 : 0.f;
+    }
+    __syncthreads();
+    // thread t of this block holds quad (base + t) % OQ
+    const int base = (int)(((long)blockIdx.x * 256) % OQ);
+    float* po = part + (long)blockIdx.x * 3 * a.OC;
+    for (int q = threadIdx.x; q < OQ; q += 256) {
+      const int t0 = ((q - base) % OQ + OQ) % OQ;
+      float cn = 0.f, cm[4] = {0.f, 0.f, 0.f, 0.f}, c2[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int t = t0; t < 256; t += OQ) {
+        const float bn = sn[t];
+        if (bn == 0.f) continue;
+        const float tot = cn + bn, fb = bn / tot;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float dd = sm[0][j][t] - cm[j];
+          c2[j] = c2[j] + sm[1][j][t] + dd * dd * cn * fb;
+          cm[j] = __builtin_fmaf(dd, fb, cm[j]);
+        }
+        cn = tot;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        po[4 * q + j] = cn;
+        po[a.OC + 4 * q + j] = cm[j];
+        po[2 * a.OC + 4 * q + j] = c2[j];
+      }
+    }
   }
 }
 
@@ -363,12 +423,31 @@ __global__ __launch_bounds__(64) void dwconv_wgrad_kernel(WgArgs a, int mult,
 
 int out_extent(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
 
+long dw_blocks(const DwArgs& a) {
+  const long items = (long)(a.OC / 4) * (((long)a.N * a.OH * a.OW + kDwPix - 1) / kDwPix);
+  return (items + 255) / 256;
+}
+
+bool dw_stats_form(const DwArgs& a) {
+  return a.mult == 1 && ((a.R == 3 && a.S == 3) || (a.R == 5 && a.S == 5));
+}
+
 template <bool DGRAD>
 void dw_launch(const DwArgs& a, const float* in, const float* w, const float* bias, float* out,
-               bool relu, bool accumulate, hipStream_t s) {
-  const long items = (long)(a.OC / 4) * (((long)a.N * a.OH * a.OW + kDwPix - 1) / kDwPix);
-  const dim3 grid((unsigned)((items + 255) / 256));
+               bool relu, bool accumulate, hipStream_t s, float* part = nullptr) {
+  const dim3 grid((unsigned)dw_blocks(a));
   const int rl = relu ? 1 : 0, ac = accumulate ? 1 : 0;
+  if constexpr (!DGRAD) {
+    if (part != nullptr) {  // statistics epilogue: its own instantiation, same output
+      if (a.R == 3)
+        hipLaunchKernelGGL((dwconv_kernel<false, 3, 3, true>), grid, dim3(256), 0, s, a, in, w,
+                           bias, out, rl, ac, part);
+      else
+        hipLaunchKernelGGL((dwconv_kernel<false, 5, 5, true>), grid, dim3(256), 0, s, a, in, w,
+                           bias, out, rl, ac, part);
+      return;
+    }
+  }
   if (a.mult == 1 && a.R == 3 && a.S == 3)
     hipLaunchKernelGGL((dwconv_kernel<DGRAD, 3, 3>), grid, dim3(256), 0, s, a, in, w, bias, out,
                        rl, ac);
@@ -399,13 +478,24 @@ int conv_group_family(const GroupConvGeom& g) {
   return (Cg % 4 == 0 && Kg % 4 == 0) ? kGroupGrouped : kGroupNone;
 }
 
-void conv_grouped_fwd(const GroupConvGeom& g, const float* x, const float* w, const float* bias,
-                      bool relu, float* y, hipStream_t s) {
+int conv_dw_stats_tiles(const GroupConvGeom& g) {
+  if (conv_group_family(g) != kGroupDepthwise) return 0;
   const int P = out_extent(g.H, g.R, g.sh, g.ph), Q = out_extent(g.W, g.S, g.sw, g.pw);
+  const DwArgs a{g.N, g.H, g.W, g.C, P, Q, g.Cout, g.R, g.S, g.sh, g.sw, g.ph, g.pw,
+                 g.Cout / g.C};
+  return dw_stats_form(a) ? (int)dw_blocks(a) : 0;
+}
+
+void conv_grouped_fwd(const GroupConvGeom& g, const float* x, const float* w, const float* bias,
+                      bool relu, float* y, hipStream_t s, float* stats_part) {
+  const int P = out_extent(g.H, g.R, g.sh, g.ph), Q = out_extent(g.W, g.S, g.sw, g.pw);
+  if (stats_part != nullptr && (conv_dw_stats_tiles(g) == 0 || bias != nullptr || relu))
+    throw std::runtime_error("conv_grouped_fwd: statistics need the register-tap depthwise "
+                             "forward (3x3 / 5x5, multiplier 1) without bias or ReLU");
   if (conv_group_family(g) == kGroupDepthwise) {
     const DwArgs a{g.N, g.H, g.W, g.C, P, Q, g.Cout, g.R, g.S, g.sh, g.sw, g.ph, g.pw,
                    g.Cout / g.C};
-    dw_launch<false>(a, x, w, bias, y, relu, false, s);
+    dw_launch<false>(a, x, w, bias, y, relu, false, s, stats_part);
   } else {
     const GcArgs a{g.N, g.H, g.W, g.C, P, Q, g.Cout, g.R, g.S, g.sh, g.sw, g.ph, g.pw,
                    g.C / g.groups, g.Cout / g.groups};

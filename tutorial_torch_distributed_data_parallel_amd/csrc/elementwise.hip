@@ -130,6 +130,86 @@ int relu_bias_slices(int B, int N, int num_cus) {
   return sl < 1 ? 1 : sl;
 }
 
+// ------------------------------------------------------------------ stand-alone ReLU6
+// A ReLU6 that follows no BatchNorm (the BatchNorm kernels fuse theirs, norm.hip). A thread owns
+// 8 consecutive elements: two 16-B loads, two 16-B stores and ONE gate byte (bit k = element
+// 8 t + k has slope 1, 0 < x < 6), which is all the backward reads besides dy (1/32 of y's
+// bytes). The last, partial group of 8 -- and every group when a pointer is not 16-B aligned --
+// goes element by element. Comparisons, not fmin / fmax: a NaN input stays NaN, as in F.relu6.
+namespace {
+__device__ __forceinline__ float relu6_of(float v) { return v < 0.f ? 0.f : (v > 6.f ? 6.f : v); }
+
+__global__ __launch_bounds__(256) void relu6_fwd_kernel(const float* __restrict__ x, long n,
+                                                        float* __restrict__ y,
+                                                        uint8_t* __restrict__ gate, int vec) {
+  const long groups = (n + 7) / 8;
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < groups; t += (long)gridDim.x * 256) {
+    const long i0 = 8 * t;
+    unsigned bits = 0;
+    if (vec && i0 + 8 <= n) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + i0 + 4 * h);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          o[j] = relu6_of(v[j]);
+          bits |= (v[j] > 0.f && v[j] < 6.f) ? (1u << (4 * h + j)) : 0u;
+        }
+        *reinterpret_cast<f32x4*>(y + i0 + 4 * h) = o;
+      }
+    } else {
+      for (int k = 0; k < 8 && i0 + k < n; ++k) {
+        const float v = x[i0 + k];
+        y[i0 + k] = relu6_of(v);
+        bits |= (v > 0.f && v < 6.f) ? (1u << k) : 0u;
+      }
+    }
+    gate[t] = (uint8_t)bits;
+  }
+}
+
+__global__ __launch_bounds__(256) void relu6_bwd_kernel(const float* __restrict__ dy,
+                                                        const uint8_t* __restrict__ gate, long n,
+                                                        float* __restrict__ dx, int vec) {
+  const long groups = (n + 7) / 8;
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < groups; t += (long)gridDim.x * 256) {
+    const long i0 = 8 * t;
+    const unsigned bits = gate[t];
+    if (vec && i0 + 8 <= n) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 d = *reinterpret_cast<const f32x4*>(dy + i0 + 4 * h);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d[j] = ((bits >> (4 * h + j)) & 1u) ? d[j] : 0.f;
+        *reinterpret_cast<f32x4*>(dx + i0 + 4 * h) = d;
+      }
+    } else {
+      for (int k = 0; k < 8 && i0 + k < n; ++k)
+        dx[i0 + k] = ((bits >> k) & 1u) ? dy[i0 + k] : 0.f;
+    }
+  }
+}
+
+inline unsigned relu6_grid(long n) {
+  long g = ((n + 7) / 8 + 255) / 256;
+  if (g > 8192) g = 8192;
+  return (unsigned)(g < 1 ? 1 : g);
+}
+}  // namespace
+
+void relu6_fwd(const float* x, long n, float* y, uint8_t* gate, hipStream_t s) {
+  if (n <= 0) return;
+  const int vec = ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
+  hipLaunchKernelGGL(relu6_fwd_kernel, dim3(relu6_grid(n)), dim3(256), 0, s, x, n, y, gate, vec);
+}
+
+void relu6_bwd(const float* dy, const uint8_t* gate, long n, float* dx, hipStream_t s) {
+  if (n <= 0) return;
+  const int vec = ((((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0;
+  hipLaunchKernelGGL(relu6_bwd_kernel, dim3(relu6_grid(n)), dim3(256), 0, s, dy, gate, n, dx, vec);
+}
+
 }  // namespace tdp
 
 // ------------------------------------------------------------------ batch gather

@@ -222,8 +222,13 @@ struct GroupConvPlan {
 };
 int conv_group_family(const GroupConvGeom& g);  // kGroupNone: neither family takes the shape
 // y = relu?(conv(x, w) + bias)
+// stats_part (optional; depthwise 3x3 / 5x5 with multiplier 1, no bias, no ReLU): also the
+// output's BatchNorm statistics, [T][3][Cout] (count, mean, M2) per block and channel with
+// T = conv_dw_stats_tiles(g) (0: the geometry has no statistics form) -- the partials
+// bn_moments_partials merges. y is bitwise what the call without it writes.
+int conv_dw_stats_tiles(const GroupConvGeom& g);
 void conv_grouped_fwd(const GroupConvGeom& g, const float* x, const float* w, const float* bias,
-                      bool relu, float* y, hipStream_t s);
+                      bool relu, float* y, hipStream_t s, float* stats_part = nullptr);
 // dx = conv^T(dy, w) (+ dx when accumulate); strided gradients gather directly
 void conv_grouped_dgrad(const GroupConvGeom& g, const float* dy, const float* w, float* dx,
                         bool accumulate, hipStream_t s);
@@ -338,6 +343,11 @@ void relu_bias_bwd_ws(const float* dy, const float* y, int B, int N, long ld, fl
                       float* db, float beta_db, float* part, int slices, hipStream_t s,
                       float gscale = 1.f);  // g = gscale * dy * (y > 0) (db unscaled)
 void fill_f32(float* x, long n, float v, hipStream_t s);
+// Stand-alone ReLU6: y = min(max(x, 0), 6) over n floats, and the backward's gate as one bit per
+// element (bit i & 7 of gate[i >> 3] set exactly when 0 < x[i] < 6; (n + 7) / 8 bytes). A NaN
+// input stays NaN. relu6_bwd: dx = gate ? dy : 0.
+void relu6_fwd(const float* x, long n, float* y, uint8_t* gate, hipStream_t s);
+void relu6_bwd(const float* dy, const uint8_t* gate, long n, float* dx, hipStream_t s);
 // 4-D strided copy over dst's logical shape; elements outside src's shape are written as 0
 // (accumulate: dst += src, and elements outside src's shape are left alone)
 struct Copy4D {
@@ -382,20 +392,23 @@ void bn_moments(const float* x, int N, int C, int HW, int splits, float* ws, flo
 void bn_merge(const float* gathered, int R, int C, float eps, float momentum, float* mean,
               float* invstd, float* running_mean, float* running_var, int64_t* num_batches,
               hipStream_t s);
-// y = (x - mean) * invstd * w + b (optional ReLU). w/b may be null (affine=False).
+// Fused activation `relu` of every forward below: 0 none, 1 ReLU, 2 ReLU6 (min(max(y, 0), 6)),
+// applied after the optional residual add. A bool converts to 0 / 1.
+// y = (x - mean) * invstd * w + b (optional activation). w/b may be null (affine=False).
 // residual (optional, [rows, C] form only): y = relu?(bn(x) + residual), the ResNet join
-// mask_out (optional, [rows, C] form with relu): the ReLU mask as one byte per 4 channels (bit j =
-// channel 4q+j > 0) -- what the backward reads instead of y (1/16 of the bytes)
+// mask_out (optional, [rows, C] form with relu): the activation mask as one byte per 4 channels
+// (bit j = channel 4q+j has slope 1: v > 0 under ReLU, 0 < v < 6 under ReLU6, v the value before
+// the clamp) -- what the backward reads instead of y (1/16 of the bytes)
 // planes_out (optional, [rows, C] form): the output's bf16 split planes [3][rows][C] too
 void bn_elemt(const float* x, const float* mean, const float* invstd, const float* w,
-              const float* b, int N, int C, int HW, bool relu, float* y, hipStream_t s,
+              const float* b, int N, int C, int HW, int relu, float* y, hipStream_t s,
               const float* residual = nullptr, uint8_t* mask_out = nullptr,
               uint16_t* planes_out = nullptr);
 // One rank (no gather): normalise [N][C] from this rank's moments [mean | var | count] and do
 // bn_merge's work in the same launch (stats [mean | invstd | count] out, running stats, the
 // batch counter). false = not the [rows, C % 4] form (nothing launched).
 bool bn_elemt_local(const float* x, const float* moments, const float* w, const float* b, int N,
-                    int C, bool relu, float eps, float momentum, float* stats, float* rmean,
+                    int C, int relu, float eps, float momentum, float* stats, float* rmean,
                     float* rvar, int64_t* nbt, float* y, uint8_t* mask_out, uint16_t* planes_out,
                     hipStream_t s, const float* residual = nullptr);
 // part [T][3][C] per-row-tile (count, mean, M2) -> mean, var (biased), count (= cnt): the
@@ -405,27 +418,28 @@ void bn_moments_partials(const float* part, int T, int C, float* ws, float* mean
 long bn_partials_ws_floats(int T, int C);
 // eval: y = (x - rmean) * rsqrt(rvar + eps) * w + b (optional ReLU)
 void bn_eval(const float* x, const float* rmean, const float* rvar, const float* w,
-             const float* b, int N, int C, int HW, float eps, bool relu, float* y, hipStream_t s);
+             const float* b, int N, int C, int HW, float eps, int relu, float* y, hipStream_t s);
 // sums[0:C] = sum dy, sums[C:2C] = sum dy*(x-mean), with dy masked by (y > 0) when y != null
-// (fused ReLU). dw/db (optional, accumulate when beta != 0): dw = sum_dy_xmu*invstd, db = sum_dy.
+// (fused ReLU; 0 < y < 6 when act == 2, the forward's ReLU6). dw/db (optional, accumulate when
+// beta != 0): dw = sum_dy_xmu*invstd, db = sum_dy.
 void bn_bwd_reduce(const float* dy, const float* x, const float* mean, const float* invstd,
                    const float* y_relu, int N, int C, int HW, int splits, float* ws, float* sums,
                    float* dw, float* db, float grad_beta, hipStream_t s,
-                   const uint8_t* mask = nullptr);
+                   const uint8_t* mask = nullptr, int act = 1);
 // dx = w*invstd*(dy - sum_dy/cnt - (x-mean)*invstd^2*sum_dy_xmu/cnt), sums possibly all-reduced.
 // dres (optional, [rows, C] form only): also write the masked dy -- the gradient of a fused
 // residual input
 void bn_bwd_elemt(const float* dy, const float* x, const float* mean, const float* invstd,
                   const float* w, const float* sums, const float* y_relu, const float* count,
                   int N, int C, int HW, float* dx, hipStream_t s, float* dres = nullptr,
-                  const uint8_t* mask = nullptr, uint16_t* planes_out = nullptr);
+                  const uint8_t* mask = nullptr, uint16_t* planes_out = nullptr, int act = 1);
 // One rank, a batch of rows (BatchNorm1d on [N][C], N <= kBn1dMaxRows, C % 16 == 0): the
 // statistics and the normalisation in ONE launch -- a workgroup owns 16 channels and ALL N rows,
 // so it needs nobody else's partial sums (bn_moments + bn_elemt_local otherwise). Writes y, the
 // stats [mean | invstd | count], the running statistics, the batch counter, and optionally the
 // ReLU mask / bf16 planes exactly as bn_elemt_local does. false = shape not taken (nothing ran).
 constexpr int kBn1dMaxRows = 512;
-bool bn1d_local_fwd(const float* x, const float* w, const float* b, int N, int C, bool relu,
+bool bn1d_local_fwd(const float* x, const float* w, const float* b, int N, int C, int relu,
                     float eps, float momentum, float* stats, float* rmean, float* rvar,
                     int64_t* nbt, float* y, uint8_t* mask_out, uint16_t* planes_out,
                     hipStream_t s);
@@ -437,7 +451,7 @@ bool bn1d_local_fwd(const float* x, const float* w, const float* b, int N, int C
 // the all-gathered [R][2C+1] moments; bn1d_sums = bn_bwd_reduce (local sums + dw / db).
 bool bn1d_moments(const float* x, int N, int C, float* moments, hipStream_t s);
 bool bn1d_gathered_fwd(const float* x, const float* gathered, int R, const float* w,
-                       const float* b, int N, int C, bool relu, float eps, float momentum,
+                       const float* b, int N, int C, int relu, float eps, float momentum,
                        float* stats, float* rmean, float* rvar, int64_t* nbt, float* y,
                        uint8_t* mask_out, uint16_t* planes_out, hipStream_t s);
 bool bn1d_sums(const float* dy, const float* x, const float* stats, int N, int C,

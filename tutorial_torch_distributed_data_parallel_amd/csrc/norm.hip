@@ -221,6 +221,26 @@ __global__ void merge_kernel(const float* __restrict__ g, int R, int C, float ep
 }
 
 // -------------------------------------------------------------------------------- elementwise
+// Fused activation of the normalised value (after the optional residual add): 0 none, 1 ReLU,
+// 2 ReLU6. The backward's gate is open exactly where the activation has slope 1: v > 0 for ReLU,
+// 0 < v < 6 for ReLU6 (zero gradient at both boundaries, as torch's hardtanh_backward), judged on
+// the value BEFORE the clamp -- so the mask-reading backward kernels serve both activations.
+constexpr int kActRelu = 1, kActRelu6 = 2;
+
+__device__ __forceinline__ float bn_act(float v, int act) {
+  if (act) v = fmaxf(v, 0.f);
+  return act == kActRelu6 ? fminf(v, 6.f) : v;
+}
+
+__device__ __forceinline__ bool bn_gate(float v, int act) {
+  return v > 0.f && (act != kActRelu6 || v < 6.f);
+}
+
+__device__ __forceinline__ uint8_t bn_mask4(float v0, float v1, float v2, float v3, int act) {
+  return (uint8_t)((bn_gate(v0, act) ? 1 : 0) | (bn_gate(v1, act) ? 2 : 0) |
+                   (bn_gate(v2, act) ? 4 : 0) | (bn_gate(v3, act) ? 8 : 0));
+}
+
 __device__ __forceinline__ int chan_of(long i, int C, int HW) {
   return HW == 1 ? (int)(i % C) : (int)((i / HW) % C);
 }
@@ -238,22 +258,24 @@ __global__ __launch_bounds__(256) void elemt_kernel(const float* __restrict__ x,
     const float is = eval ? rsqrtf(invstd[c] + eps) : invstd[c];
     const float sc = is * (w ? w[c] : 1.f);
     float v = fmaf(x[i] - mean[c], sc, b ? b[c] : 0.f);
-    if (relu) v = fmaxf(v, 0.f);
-    y[i] = v;
+    y[i] = bn_act(v, relu);
   }
 }
 
 // -------------------------------------------------------------------------------- backward
-__device__ __forceinline__ float masked_dy(const float* dy, const float* yr, long off) {
+// `yr`: the saved activated output (null = no activation); its gate is bn_gate on the output,
+// which for a clamped value (exactly 0 or 6) is closed as it is on the pre-clamp value
+__device__ __forceinline__ float masked_dy(const float* dy, const float* yr, long off, int act) {
   const float g = dy[off];
-  return (yr && !(yr[off] > 0.f)) ? 0.f : g;
+  return (yr && !bn_gate(yr[off], act)) ? 0.f : g;
 }
 
 __global__ __launch_bounds__(256) void bwd_reduce_1d(const float* __restrict__ dy,
                                                      const float* __restrict__ x,
                                                      const float* __restrict__ mean,
                                                      const float* __restrict__ yr, int N, int C,
-                                                     int splits, float* __restrict__ part) {
+                                                     int splits, float* __restrict__ part,
+                                                     int act) {
   __shared__ float s0[4][64], s1[4][64];
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
@@ -264,7 +286,7 @@ __global__ __launch_bounds__(256) void bwd_reduce_1d(const float* __restrict__ d
     const float mu = mean[c];
     for (long n = b + g; n < e; n += 4) {
       const long off = n * C + c;
-      const float d = masked_dy(dy, yr, off);
+      const float d = masked_dy(dy, yr, off, act);
       a += d;
       m = fmaf(d, x[off] - mu, m);
     }
@@ -284,7 +306,7 @@ __global__ __launch_bounds__(256) void bwd_reduce_2d(const float* __restrict__ d
                                                      const float* __restrict__ mean,
                                                      const float* __restrict__ yr, int N, int C,
                                                      int HW, int splits,
-                                                     float* __restrict__ part) {
+                                                     float* __restrict__ part, int act) {
   __shared__ float red[4];
   const int c = blockIdx.x;
   long b, e;
@@ -294,7 +316,7 @@ __global__ __launch_bounds__(256) void bwd_reduce_2d(const float* __restrict__ d
   for (long i = b + threadIdx.x; i < e; i += 256) {
     const long n = i / HW, hw = i - n * HW;
     const long off = (n * C + c) * HW + hw;
-    const float d = masked_dy(dy, yr, off);
+    const float d = masked_dy(dy, yr, off, act);
     a += d;
     m = fmaf(d, x[off] - mu, m);
   }
@@ -346,7 +368,7 @@ __global__ __launch_bounds__(256) void bwd_elemt_kernel(
     const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ w,
     const float* __restrict__ sums, const float* __restrict__ yr, const float* __restrict__ cnt,
-    long total, int C, int HW, float* __restrict__ dx) {
+    long total, int C, int HW, float* __restrict__ dx, int act) {
   const float inv_count = 1.f / cnt[0];
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total;
        i += (long)gridDim.x * blockDim.x) {
@@ -354,7 +376,7 @@ __global__ __launch_bounds__(256) void bwd_elemt_kernel(
     const float is = invstd[c];
     const float mdy = sums[c] * inv_count;
     const float mdyx = sums[C + c] * inv_count;
-    const float d = masked_dy(dy, yr, i);
+    const float d = masked_dy(dy, yr, i, act);
     const float v = (d - mdy - (x[i] - mean[c]) * is * is * mdyx) * is * (w ? w[c] : 1.f);
     dx[i] = v;
   }
@@ -456,7 +478,8 @@ __global__ __launch_bounds__(kRedT) void bwd_reduce_rows4(const float* __restric
                                                           const float* __restrict__ yr, int N,
                                                           int C, int splits,
                                                           float* __restrict__ part,
-                                                          const uint8_t* __restrict__ mk) {
+                                                          const uint8_t* __restrict__ mk,
+                                                          int kind) {
   __shared__ float sh[2][4096];
   int CB, LPR, RPW;
   rows4_layout(C, CB, LPR, RPW, kRedT);
@@ -480,7 +503,7 @@ __global__ __launch_bounds__(kRedT) void bwd_reduce_rows4(const float* __restric
       } else if (yr) {
         const f32x4 yv = *reinterpret_cast<const f32x4*>(yr + off);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = yv[j] > 0.f ? d[j] : 0.f;
+        for (int j = 0; j < 4; ++j) d[j] = bn_gate(yv[j], kind) ? d[j] : 0.f;
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -576,19 +599,19 @@ __global__ __launch_bounds__(256) void elemt_rows4(const float* __restrict__ x,
     // residual join (ResNet: relu(bn3(conv3) + identity)) fused into the normalisation
     const f32x4 rv = res ? *reinterpret_cast<const f32x4*>(res + r * C + c)
                          : f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 o;
+    f32x4 o, pre;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float q = fmaf(v[j] - mn[j], sc[j], sf[j]) + rv[j];
-      o[j] = relu ? fmaxf(q, 0.f) : q;
+      pre[j] = q;
+      o[j] = bn_act(q, relu);
     }
     *reinterpret_cast<f32x4*>(y + r * C + c) = o;
     // bf16 split planes of the output for a consuming skinny Linear (planes GEMM)
     if (pl) store_planes4(pl + r * C + c, (long)N * C, o[0], o[1], o[2], o[3]);
-    // ReLU mask for the backward: one byte per 4 channels (64 lanes: 64 consecutive bytes)
-    if (mk)
-      mk[(r * C + c) >> 2] = (uint8_t)((o[0] > 0.f ? 1 : 0) | (o[1] > 0.f ? 2 : 0) |
-                                       (o[2] > 0.f ? 4 : 0) | (o[3] > 0.f ? 8 : 0));
+    // activation mask for the backward: one byte per 4 channels (64 lanes: 64 consecutive
+    // bytes), from the pre-clamp value (bn_gate)
+    if (mk) mk[(r * C + c) >> 2] = bn_mask4(pre[0], pre[1], pre[2], pre[3], relu);
   }
 }
 
@@ -599,7 +622,7 @@ __global__ __launch_bounds__(256) void bwd_elemt_rows4(
     const float* __restrict__ invstd, const float* __restrict__ w,
     const float* __restrict__ sums, const float* __restrict__ yr, const float* __restrict__ cnt,
     int N, int C, int splits, float* __restrict__ dx, float* __restrict__ dres,
-    const uint8_t* __restrict__ mk, uint16_t* __restrict__ pl) {
+    const uint8_t* __restrict__ mk, uint16_t* __restrict__ pl, int act) {
   int CB, LPR, RPW;
   rows4_layout(C, CB, LPR, RPW);
   const int t = threadIdx.x, cq = t % LPR, rg = t / LPR;
@@ -633,7 +656,7 @@ __global__ __launch_bounds__(256) void bwd_elemt_rows4(
     } else if (yr) {
       const f32x4 yv = *reinterpret_cast<const f32x4*>(yr + off);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) d[j] = yv[j] > 0.f ? d[j] : 0.f;
+      for (int j = 0; j < 4; ++j) d[j] = bn_gate(yv[j], act) ? d[j] : 0.f;
     }
     f32x4 o;
 #pragma unroll
@@ -767,17 +790,16 @@ __global__ __launch_bounds__(256) void bn1d_local_fwd_kernel(
   for (int i = 0; i < IT; ++i) {
     const int r = rg + kB1Lanes * i;
     if (r >= N) continue;
-    f32x4 o;
+    f32x4 o, pre;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float t = fmaf(v[i][j] - mean[j], sc[j], sf[j]);
-      o[j] = relu ? fmaxf(t, 0.f) : t;
+      pre[j] = t;
+      o[j] = bn_act(t, relu);
     }
     *reinterpret_cast<f32x4*>(y + (long)r * C + c) = o;
     if (pl) store_planes4(pl + (long)r * C + c, (long)N * C, o[0], o[1], o[2], o[3]);
-    if (mk)
-      mk[((long)r * C + c) >> 2] = (uint8_t)((o[0] > 0.f ? 1 : 0) | (o[1] > 0.f ? 2 : 0) |
-                                             (o[2] > 0.f ? 4 : 0) | (o[3] > 0.f ? 8 : 0));
+    if (mk) mk[((long)r * C + c) >> 2] = bn_mask4(pre[0], pre[1], pre[2], pre[3], relu);
   }
 }
 
@@ -1001,25 +1023,25 @@ void bn_merge(const float* gathered, int R, int C, float eps, float momentum, fl
 }
 
 bool bn_elemt_local(const float* x, const float* moments, const float* w, const float* b, int N,
-                    int C, bool relu, float eps, float momentum, float* stats, float* rmean,
+                    int C, int relu, float eps, float momentum, float* stats, float* rmean,
                     float* rvar, int64_t* nbt, float* y, uint8_t* mask_out, uint16_t* planes_out,
                     hipStream_t s, const float* residual) {
   if (!rows4_ok(C, 1, {x, y, moments, w, b, stats, residual})) return false;
   const int sp = rows4_ew_splits(N, C);
   hipLaunchKernelGGL(elemt_rows4, dim3(rows4_nblk(C), sp), dim3(256), 0, s, x, moments,
-                     moments + C, w, b, N, C, sp, relu ? 1 : 0, 0, eps, residual, y,
+                     moments + C, w, b, N, C, sp, relu, 0, eps, residual, y,
                      relu ? mask_out : nullptr, planes_out,
                      LocalMerge{stats, rmean, rvar, nbt, momentum});
   return true;
 }
 
 void bn_elemt(const float* x, const float* mean, const float* invstd, const float* w,
-              const float* b, int N, int C, int HW, bool relu, float* y, hipStream_t s,
+              const float* b, int N, int C, int HW, int relu, float* y, hipStream_t s,
               const float* residual, uint8_t* mask_out, uint16_t* planes_out) {
   if (rows4_ok(C, HW, {x, y, mean, invstd, w, b, residual})) {
     const int sp = rows4_ew_splits(N, C);
     hipLaunchKernelGGL(elemt_rows4, dim3(rows4_nblk(C), sp), dim3(256), 0, s, x, mean, invstd, w,
-                       b, N, C, sp, relu ? 1 : 0, 0, 0.f, residual, y, relu ? mask_out : nullptr,
+                       b, N, C, sp, relu, 0, 0.f, residual, y, relu ? mask_out : nullptr,
                        planes_out, LocalMerge{});
     return;
   }
@@ -1028,38 +1050,39 @@ void bn_elemt(const float* x, const float* mean, const float* invstd, const floa
   if (planes_out) throw std::runtime_error("bn_elemt: planes need the [rows, C%4] form");
   const long total = (long)N * C * HW;
   hipLaunchKernelGGL(elemt_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, mean, invstd, w, b,
-                     total, C, HW, relu ? 1 : 0, 0, 0.f, y);
+                     total, C, HW, relu, 0, 0.f, y);
 }
 
 void bn_eval(const float* x, const float* rmean, const float* rvar, const float* w,
-             const float* b, int N, int C, int HW, float eps, bool relu, float* y, hipStream_t s) {
+             const float* b, int N, int C, int HW, float eps, int relu, float* y, hipStream_t s) {
   if (rows4_ok(C, HW, {x, y})) {
     const int sp = rows4_ew_splits(N, C);
     hipLaunchKernelGGL(elemt_rows4, dim3(rows4_nblk(C), sp), dim3(256), 0, s, x, rmean, rvar, w,
-                       b, N, C, sp, relu ? 1 : 0, 1, eps, (const float*)nullptr, y,
+                       b, N, C, sp, relu, 1, eps, (const float*)nullptr, y,
                        (uint8_t*)nullptr, (uint16_t*)nullptr, LocalMerge{});
     return;
   }
   const long total = (long)N * C * HW;
   hipLaunchKernelGGL(elemt_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, rmean, rvar, w, b,
-                     total, C, HW, relu ? 1 : 0, 1, eps, y);
+                     total, C, HW, relu, 1, eps, y);
 }
 
 void bn_bwd_reduce(const float* dy, const float* x, const float* mean, const float* invstd,
                    const float* y_relu, int N, int C, int HW, int splits, float* ws, float* sums,
-                   float* dw, float* db, float grad_beta, hipStream_t s, const uint8_t* mask) {
+                   float* dw, float* db, float grad_beta, hipStream_t s, const uint8_t* mask,
+                   int act) {
   // partials always go through ws (2*C*splits floats); the final kernel also writes dw/db
   if (rows4_ok(C, HW, {dy, x, y_relu, mean}))
     hipLaunchKernelGGL(bwd_reduce_rows4, dim3(rows4_nblk(C), splits), dim3(kRedT), 0, s, dy, x,
-                       mean, y_relu, N, C, splits, ws, mask);
+                       mean, y_relu, N, C, splits, ws, mask, act);
   else if (mask)
     throw std::runtime_error("bn_bwd_reduce: a ReLU mask needs the [rows, C%4] form");
   else if (HW == 1)
     hipLaunchKernelGGL(bwd_reduce_1d, dim3((C + 63) / 64, splits), dim3(256), 0, s, dy, x, mean,
-                       y_relu, N, C, splits, ws);
+                       y_relu, N, C, splits, ws, act);
   else
     hipLaunchKernelGGL(bwd_reduce_2d, dim3(C, splits), dim3(256), 0, s, dy, x, mean, y_relu, N, C,
-                       HW, splits, ws);
+                       HW, splits, ws, act);
   hipLaunchKernelGGL(bwd_reduce_final, dim3((C + 15) / 16), dim3(256), 0, s, ws, C, splits,
                      invstd, sums, dw, db, grad_beta);
 }
@@ -1067,11 +1090,12 @@ void bn_bwd_reduce(const float* dy, const float* x, const float* mean, const flo
 void bn_bwd_elemt(const float* dy, const float* x, const float* mean, const float* invstd,
                   const float* w, const float* sums, const float* y_relu, const float* count,
                   int N, int C, int HW, float* dx, hipStream_t s, float* dres,
-                  const uint8_t* mask, uint16_t* planes_out) {
+                  const uint8_t* mask, uint16_t* planes_out, int act) {
   if (rows4_ok(C, HW, {dy, x, y_relu, dx, dres})) {
     const int sp = rows4_ew_splits(N, C);
     hipLaunchKernelGGL(bwd_elemt_rows4, dim3(rows4_nblk(C), sp), dim3(256), 0, s, dy, x, mean,
-                       invstd, w, sums, y_relu, count, N, C, sp, dx, dres, mask, planes_out);
+                       invstd, w, sums, y_relu, count, N, C, sp, dx, dres, mask, planes_out,
+                       act);
     return;
   }
   if (planes_out) throw std::runtime_error("bn_bwd_elemt: planes need the [rows, C%4] form");
@@ -1079,10 +1103,10 @@ void bn_bwd_elemt(const float* dy, const float* x, const float* mean, const floa
   if (mask) throw std::runtime_error("bn_bwd_elemt: a ReLU mask needs the [rows, C%4] form");
   const long total = (long)N * C * HW;
   hipLaunchKernelGGL(bwd_elemt_kernel, dim3(ew_grid(total)), dim3(256), 0, s, dy, x, mean, invstd,
-                     w, sums, y_relu, count, total, C, HW, dx);
+                     w, sums, y_relu, count, total, C, HW, dx, act);
 }
 
-bool bn1d_local_fwd(const float* x, const float* w, const float* b, int N, int C, bool relu,
+bool bn1d_local_fwd(const float* x, const float* w, const float* b, int N, int C, int relu,
                     float eps, float momentum, float* stats, float* rmean, float* rvar,
                     int64_t* nbt, float* y, uint8_t* mask_out, uint16_t* planes_out,
                     hipStream_t s) {
@@ -1090,7 +1114,7 @@ bool bn1d_local_fwd(const float* x, const float* w, const float* b, int N, int C
   for (const void* q : {(const void*)x, (const void*)y, (const void*)w, (const void*)b})
     if (q && ((uintptr_t)q & 15)) return false;
   const dim3 g(C / kB1Cols), t(256);
-  const int r = relu ? 1 : 0;
+  const int r = relu;
   uint8_t* mk = relu ? mask_out : nullptr;
 #define B1F(IT) hipLaunchKernelGGL((bn1d_local_fwd_kernel<IT, kB1Local>), g, t, 0, s, x, w, b, N, \
                                    C, r, eps, momentum, stats, rmean, rvar, nbt, y, mk, \
@@ -1139,14 +1163,14 @@ bool bn1d_moments(const float* x, int N, int C, float* moments, hipStream_t s) {
 }
 
 bool bn1d_gathered_fwd(const float* x, const float* gathered, int R, const float* w,
-                       const float* b, int N, int C, bool relu, float eps, float momentum,
+                       const float* b, int N, int C, int relu, float eps, float momentum,
                        float* stats, float* rmean, float* rvar, int64_t* nbt, float* y,
                        uint8_t* mask_out, uint16_t* planes_out, hipStream_t s) {
   if (N < 1 || N > kBn1dMaxRows || C % kB1Cols || R < 1) return false;
   for (const void* q : {(const void*)x, (const void*)y, (const void*)w, (const void*)b})
     if (q && ((uintptr_t)q & 15)) return false;
   const dim3 g(C / kB1Cols), t(256);
-  const int r = relu ? 1 : 0;
+  const int r = relu;
   uint8_t* mk = relu ? mask_out : nullptr;
 #define B1G(IT) hipLaunchKernelGGL((bn1d_local_fwd_kernel<IT, kB1Gathered>), g, t, 0, s, x, w, b, \
                                    N, C, r, eps, momentum, stats, rmean, rvar, nbt, y, mk, \

@@ -28,6 +28,10 @@ def build_model(name: str, num_classes: int = 10, device=None) -> torch.nn.Modul
         from .resnet import resnext50_32x4d
 
         return resnext50_32x4d(num_classes=num_classes, device=device)
+    if name in ("mobilenet_v2", "mobilenetv2"):
+        from .mobilenet import mobilenet_v2
+
+        return mobilenet_v2(num_classes=num_classes, device=device)
     if name in ("mixer_s16", "mixer_b16"):
         from . import mixer
 

@@ -69,6 +69,13 @@ class ReLU(nn.ReLU):
         return torch.relu(x)
 
 
+class ReLU6(nn.ReLU6):
+    """Standalone ReLU6 (``ops.relu6``); after a BatchNorm use its ``relu6=True`` instead."""
+
+    def forward(self, x):
+        return ops.relu6(x)
+
+
 class MaxPool2d(nn.MaxPool2d):
     def forward(self, x):
         return ops.max_pool2d(x, self.kernel_size, self.stride, self.padding)
@@ -88,23 +95,30 @@ class _NativeBN(nn.modules.batchnorm._BatchNorm):
     """Shared forward for BatchNorm{1,2}d / SyncBatchNorm."""
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
-                 track_running_stats=True, relu: bool = False, device=None, dtype=None):
+                 track_running_stats=True, relu: bool = False, device=None, dtype=None,
+                 relu6: bool = False):
+        if relu and relu6:
+            raise ValueError("BatchNorm: relu and relu6 are mutually exclusive")
         super().__init__(num_features, eps, momentum, affine, track_running_stats,
                          device=device, dtype=dtype)
         self.relu = relu
+        self.relu6 = relu6  # fused min(max(y, 0), 6) (MobileNetV2's activation)
         self._nbt = 0  # host mirror of num_batches_tracked: no device->host sync per step
 
     def _group(self):
         return None
 
     def relu_join(self, x, residual, grad_into=None):
-        """``relu(bn(x) + residual)`` as one normalisation pass (ResNet's residual join);
+        """``relu(bn(x) + residual)`` (ReLU6 on a ``relu6`` module) as one normalisation pass
+        (ResNet's residual join);
         ``grad_into``: the residual's gradient goes into that ``SharedGrad``."""
         return self.forward(x, residual, relu=True, residual_grad_into=grad_into)
 
     def forward(self, x, residual=None, relu=None, residual_grad_into=None):
-        """``relu?(bn(x) [+ residual])``; ``residual`` fuses a residual join into the
-        normalisation (ResNet's ``relu(bn3(conv3(.)) + identity)``, one pass instead of two)."""
+        """``act?(bn(x) [+ residual])``; ``residual`` fuses a residual join into the
+        normalisation (ResNet's ``relu(bn3(conv3(.)) + identity)``, one pass instead of two).
+        ``relu`` switches the module's activation (ReLU, or ReLU6 on a ``relu6`` module) on or
+        off for this call."""
         self._check_input_dim(x)
         use_batch = self.training or not self.track_running_stats
         factor = 0.0
@@ -118,14 +132,19 @@ class _NativeBN(nn.modules.batchnorm._BatchNorm):
             factor = (1.0 / self._nbt) if self.momentum is None else self.momentum
         rm = self.running_mean if (not self.training or self.track_running_stats) else None
         rv = self.running_var if (not self.training or self.track_running_stats) else None
+        # `relu` switches the module's own activation off (False) or on (True): on a relu6
+        # module "on" is the ReLU6, never a silent plain ReLU
+        own6 = getattr(self, "relu6", False)
+        on = (self.relu or own6) if relu is None else bool(relu)
         return ops.batch_norm(x, rm, rv, self.weight, self.bias, training=use_batch,
-                              momentum=factor, eps=self.eps,
-                              relu=self.relu if relu is None else relu,
+                              momentum=factor, eps=self.eps, relu=on and not own6,
                               group=self._group() if use_batch else None, residual=residual,
-                              num_batches_tracked=nbt, residual_grad_into=residual_grad_into)
+                              num_batches_tracked=nbt, residual_grad_into=residual_grad_into,
+                              relu6=on and own6)
 
     def extra_repr(self) -> str:
-        return super().extra_repr() + (", relu=True" if self.relu else "")
+        return super().extra_repr() + (", relu=True" if self.relu else "") + \
+            (", relu6=True" if getattr(self, "relu6", False) else "")
 
 
 class BatchNorm1d(_NativeBN):
@@ -162,7 +181,8 @@ class SyncBatchNorm(_NativeBN):
         out = module
         if isinstance(module, nn.modules.batchnorm._BatchNorm) and not isinstance(module, cls):
             out = cls(module.num_features, module.eps, module.momentum, module.affine,
-                      module.track_running_stats, relu=getattr(module, "relu", False))
+                      module.track_running_stats, relu=getattr(module, "relu", False),
+                      relu6=getattr(module, "relu6", False))
             if module.affine:
                 with torch.no_grad():
                     out.weight = module.weight

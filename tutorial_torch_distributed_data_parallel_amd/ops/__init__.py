@@ -1,5 +1,5 @@
 """Differentiable ops over the native gfx950 kernels (CPU tensors use the torch reference)."""
-from .activation import gelu
+from .activation import gelu, relu6
 from .conv import conv2d
 from .layernorm import layer_norm
 from .linear import linear
@@ -10,4 +10,4 @@ from .pool import adaptive_avg_pool2d, add_relu, dropout, flatten, max_pool2d
 
 __all__ = ["linear", "conv2d", "max_pool2d", "adaptive_avg_pool2d", "dropout", "add_relu",
            "cross_entropy", "linear_cross_entropy", "count_correct", "batch_norm", "backward", "seed_grad", "flatten",
-           "autocast", "is_autocast_enabled", "layer_norm", "gelu"]
+           "autocast", "is_autocast_enabled", "layer_norm", "gelu", "relu6"]

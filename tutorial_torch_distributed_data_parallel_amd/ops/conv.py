@@ -26,8 +26,13 @@ VALU, the same channels_last weight memory in all three passes, the weight gradi
 straight into the parameter's gradient slot. Two families: grouped (Cin/groups and Cout/groups
 multiples of 4; ResNeXt, two-tower AlexNet) and depthwise (groups == Cin, Cout = m * Cin,
 Cin % 4 == 0; a register-tap stencil). Any other channel combination raises
-``NotImplementedError``. No statistics epilogue (``bn_stats`` produces nothing) and no bf16 form:
-inside ``tdp.autocast`` a grouped convolution stays fp32, bitwise equal to the result outside it.
+``NotImplementedError``. No bf16 form: inside ``tdp.autocast`` a grouped convolution stays fp32,
+bitwise equal to the result outside it. ``bn_stats`` produces nothing for the grouped family and
+for the generic depthwise form; the register-tap depthwise forward (3x3 / 5x5, channel multiplier
+1, no bias, no fused ReLU) has a statistics epilogue behind ``DW_BN_STATS``: each block reduces
+its own pixels per channel in LDS in a fixed order and writes one (count, mean, M2) partial per
+(block, channel), the ``[T, 3, C]`` layout ``bn_moments_partials`` consumes, so BatchNorm skips its
+moments pass over the output. The output is bitwise the one without the epilogue.
 ``groups == 1`` never reaches this code.
 
 Mixed precision -- inside ``tdp.autocast`` (ops/precision.py) a float32 convolution the NHWC
@@ -246,6 +251,11 @@ def _dgrad_phases(C, g, wt, x_shape, R, S, sh, sw, ph, pw, into=None, bf16=False
 
 FORCE_NCHW = False  # tests: route every conv through the NCHW fallback kernels
 AUTOCAST_FP32_CONV = False  # A/B measurement: convolutions stay fp32 inside tdp.autocast
+# bn_stats on a register-tap depthwise forward emits the BatchNorm statistics from the kernel
+# (False: BatchNorm runs its moments pass, A/B measurement). On: over MobileNetV2's depthwise
+# layers forward + epilogue + merge takes 475 us against 515 us for forward + moments pass, and
+# the eager step is not slower (profiles/r18/mobilenet_v2.md).
+DW_BN_STATS = True
 
 
 def _bf16r(t: torch.Tensor) -> torch.Tensor:
@@ -310,11 +320,19 @@ class _ConvGroupedFn(torch.autograd.Function):
     gradient slot; the ReLU mask and the bias gradient are the shared ``relu_bias_bwd`` pass."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, groups: int, relu: bool, sink=None):
+    def forward(ctx, x, weight, bias, stride, padding, groups: int, relu: bool, sink=None,
+                stats_box=None):
         C = native()
         xc = _as_cl(C, x)
         wt = _as_cl(C, weight)  # the parameter itself when it is stored channels_last
-        y = C.conv_grouped_fwd(xc, wt, bias, *stride, *padding, groups, relu)
+        if stats_box is not None:
+            # depthwise, no bias, no ReLU: the stencil also emits the per-block BN statistics
+            # (None when the geometry has no statistics form)
+            r = C.conv_dw_fwd_stats(xc, wt, *stride, *padding, groups)
+            y = r[0]
+            stats_box.append(r[1] if len(r) > 1 else None)
+        else:
+            y = C.conv_grouped_fwd(xc, wt, bias, *stride, *padding, groups, relu)
         ctx.geom = (*stride, *padding, groups)
         ctx.sink = sink
         ctx.relu = relu
@@ -356,7 +374,7 @@ class _ConvGroupedFn(torch.autograd.Function):
                                       accumulate=acc is not None)
             if sink is not None and acc is None:
                 dx = sink.deposit(dx)
-        return dx, dw, db, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None
 
 
 def _nhwc_ok(x, weight, stride):
@@ -386,8 +404,9 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
 
     ``groups > 1``: grouped or depthwise convolution on csrc/conv_grouped.hip (``weight`` is
     torch's ``[Cout, Cin/groups, R, S]``); ``grouped_family`` states which channel counts are
-    taken, any other raises ``NotImplementedError``. ``bn_stats`` produces nothing there and the
-    convolution stays fp32 inside ``tdp.autocast``. ``dilation`` other than 1 is not supported."""
+    taken, any other raises ``NotImplementedError``. ``bn_stats`` produces nothing there -- except,
+    with ``DW_BN_STATS``, for a 3x3 / 5x5 depthwise convolution with channel multiplier 1, no bias
+    and no ReLU -- and the convolution stays fp32 inside ``tdp.autocast``. ``dilation`` other than 1 is not supported."""
     stride, padding = _pair(stride), _pair(padding)
     if _pair(dilation) != (1, 1):
         raise NotImplementedError("conv2d: dilation is not supported (dilation must be 1)")
@@ -397,8 +416,13 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
             return F.relu(y) if relu else y
         if x.dtype != torch.float32:
             raise TypeError(f"native conv2d expects float32 activations, got {x.dtype}")
-        grouped_family(x.shape[1], weight.shape[0], groups)
-        return _ConvGroupedFn.apply(x, weight, bias, stride, padding, groups, relu, grad_into)
+        family = grouped_family(x.shape[1], weight.shape[0], groups)
+        box = [] if (bn_stats and DW_BN_STATS and family == "depthwise" and bias is None
+                     and not relu) else None
+        y = _ConvGroupedFn.apply(x, weight, bias, stride, padding, groups, relu, grad_into, box)
+        if box and box[0] is not None:
+            y._tdp_bn_part = (box[0], y._version)  # ops/norm.py batch_norm consumes it
+        return y
     amp = is_autocast_enabled() and x.dtype == torch.float32 and not AUTOCAST_FP32_CONV
     if not x.is_cuda:
         if amp:

@@ -2,7 +2,7 @@
 
 Protocol (same as torch's SyncBatchNorm, TORCH/nn/modules/_functions.py:7-209):
   forward : local [mean | var | count]  --all_gather-->  count-weighted merge (+ running stats)
-            --> normalise (optionally with a fused ReLU)
+            --> normalise (optionally with a fused ReLU or ReLU6)
   backward: local [sum_dy | sum_dy_xmu] (+ local dW, dB straight into the grad arena)
             --all_reduce(sum)--> dx
 With ``group=None`` the same kernels implement plain BatchNorm (one "rank").
@@ -14,6 +14,13 @@ A batch of rows (BatchNorm1d, N <= 512 rows, C % 16 == 0) runs the whole-column 
 (``bn1d_local_fwd`` / ``bn1d_local_bwd``, the latter also applying the fused optimizer to w / b),
 ``bn1d_moments`` -> all-gather -> ``bn1d_gathered_fwd`` and ``bn1d_sums`` -> all-reduce under
 SyncBatchNorm (``set_local1d`` / ``set_sync1d`` switch back to the split kernels).
+
+Fused activation -- the kernels take ``relu`` as 0 (none), 1 (ReLU) or 2 (ReLU6,
+``min(max(y, 0), 6)``, MobileNetV2's only activation), applied after the optional residual add.
+The backward's gate is open where the activation has slope 1 (``y > 0``; ``0 < y < 6`` for ReLU6,
+zero gradient at both boundaries as in torch's ``hardtanh_backward``). The 1-byte-per-4-channels
+mask of the [rows, C % 4 == 0] form stores that gate, so the mask-reading backward kernels serve
+both; the forms that re-read the saved float output are told the kind (``act=``).
 
 Reference: the README's SyncBatchNorm pitfall (/root/reference/README.md:79-81) -- BatchNorm
 statistics must be synced across ranks, via ``convert_sync_batchnorm`` before wrapping in DDP.
@@ -27,6 +34,21 @@ import torch.nn.functional as F
 from .._native import native
 from ._grad import bias_epilogue, grad_dest, hand_off, needs
 from .linear import attach_planes, planes_input_fit
+
+
+_RELU6 = 2  # the kernels' activation kind: 0 none, 1 (True) ReLU, 2 ReLU6
+
+
+def _act(y, kind):
+    """The fused activation ``kind`` in torch ops."""
+    if kind == _RELU6:
+        return F.relu6(y)
+    return F.relu(y) if kind else y
+
+
+def _gate(y, kind):
+    """Where the activation that produced ``y`` has slope 1."""
+    return (y > 0) & (y < 6) if kind == _RELU6 else (y > 0)
 
 
 class _TorchKernels:
@@ -71,12 +93,12 @@ class _TorchKernels:
             y = y + b.view(shape)
         if residual is not None:
             y = y + residual
-        return F.relu(y) if relu else y
+        return _act(y, relu)
 
-    def bn_bwd_reduce(self, dy, x, stats, y, dw, db, beta):
+    def bn_bwd_reduce(self, dy, x, stats, y, dw, db, beta, act=1):
         C = x.shape[1]
         if y is not None:
-            dy = dy * (y > 0)
+            dy = dy * _gate(y, act)
         dv, xv = self._view(dy), self._view(x)
         s_dy = dv.sum(dim=(0, 2))
         s_dyx = (dv * (xv - stats[:C].view(1, C, 1))).sum(dim=(0, 2))
@@ -86,11 +108,11 @@ class _TorchKernels:
             db.copy_(s_dy)
         return torch.cat([s_dy, s_dyx])
 
-    def bn_bwd_elemt(self, dy, x, stats, w, sums, y, residual_grad=False):
+    def bn_bwd_elemt(self, dy, x, stats, w, sums, y, residual_grad=False, act=1):
         C = x.shape[1]
         shape = (1, C) + (1,) * (x.dim() - 2)
         if y is not None:
-            dy = dy * (y > 0)
+            dy = dy * _gate(y, act)
         cnt = stats[2 * C]
         inv = stats[C: 2 * C].view(shape)
         mdy = (sums[:C] / cnt).view(shape)
@@ -250,6 +272,8 @@ class _BatchNormFn(torch.autograd.Function):
         dw = grad_dest(w_param) if (w_param is not None and needs(ctx, 1)) else None
         db = grad_dest(b_param) if (b_param is not None and needs(ctx, 2)) else None
         mk = {} if mask is None else {"mask": mask}
+        if ctx.relu == _RELU6 and y is not None:
+            mk["act"] = _RELU6  # the saved float output is gated on 0 < y < 6
         if ctx.local1d and ctx.group is None:
             # one launch: the column sums, dw / db and dx (+ its planes) of a whole-rows batch
             pl = None
@@ -327,10 +351,18 @@ def batch_norm(x: torch.Tensor, running_mean: torch.Tensor | None,
                running_var: torch.Tensor | None, weight: torch.Tensor | None = None,
                bias: torch.Tensor | None = None, training: bool = True, momentum: float = 0.1,
                eps: float = 1e-5, relu: bool = False, group=None, residual=None,
-               num_batches_tracked=None, residual_grad_into=None) -> torch.Tensor:
-    """``relu?(batch_norm(x) [+ residual])`` over dim 1 of x ([N, C] or [N, C, *]); ``group``
-    makes it synchronous; ``num_batches_tracked`` (training) is incremented on the device;
-    ``residual_grad_into`` (a ``SharedGrad``) receives the residual's gradient."""
+               num_batches_tracked=None, residual_grad_into=None,
+               relu6: bool = False) -> torch.Tensor:
+    """``act?(batch_norm(x) [+ residual])`` over dim 1 of x ([N, C] or [N, C, *]) with ``act`` a
+    ReLU (``relu``) or a ReLU6 (``relu6``; not both); ``group`` makes it synchronous;
+    ``num_batches_tracked`` (training) is incremented on the device; ``residual_grad_into`` (a
+    ``SharedGrad``) receives the residual's gradient."""
+    if relu6:
+        if relu:
+            raise ValueError("batch_norm: relu and relu6 are mutually exclusive")
+        relu = _RELU6  # the kernels' third activation kind; bool(relu) otherwise, as before
+    else:
+        relu = bool(relu)
     if training:
         if residual is not None and x.is_cuda and not (x.shape[1] % 4 == 0 and (
                 x.dim() == 2 or _is_nhwc(x))):
@@ -338,22 +370,22 @@ def batch_norm(x: torch.Tensor, running_mean: torch.Tensor | None,
             y = _BatchNormFn.apply(x, weight, bias, running_mean, running_var, float(momentum),
                                    float(eps), False, group, None, num_batches_tracked)
             y = y + residual
-            return F.relu(y) if relu else y
+            return _act(y, relu)
         return _BatchNormFn.apply(x, weight, bias, running_mean, running_var, float(momentum),
-                                  float(eps), bool(relu), group, residual, num_batches_tracked,
+                                  float(eps), relu, group, residual, num_batches_tracked,
                                   residual_grad_into, _conv_stats(x))
     if residual is not None:
         y = batch_norm(x, running_mean, running_var, weight, bias, False, momentum, eps, False)
         y = y + residual
-        return F.relu(y) if relu else y
+        return _act(y, relu)
     if x.is_cuda and not (torch.is_grad_enabled() and (x.requires_grad or (
             weight is not None and weight.requires_grad))):
         if _is_nhwc(x):
             y2 = native().bn_eval(_rows(x), running_mean, running_var, weight, bias, float(eps),
-                                  bool(relu))
+                                  relu)
             return _unrows(y2, tuple(x.shape))
         return native().bn_eval(x.contiguous(), running_mean, running_var, weight, bias,
-                                float(eps), bool(relu))
+                                float(eps), relu)
     # inference-mode BN that must be differentiated (frozen-BN fine-tuning): a per-channel affine
     # map y = x * scale + shift, differentiated by autograd through plain elementwise ops
     shape = (1, x.shape[1]) + (1,) * (x.dim() - 2)
@@ -364,4 +396,4 @@ def batch_norm(x: torch.Tensor, running_mean: torch.Tensor | None,
     if bias is not None:
         shift = shift + bias
     y = x * scale.view(shape) + shift.view(shape)
-    return F.relu(y) if relu else y
+    return _act(y, relu)
