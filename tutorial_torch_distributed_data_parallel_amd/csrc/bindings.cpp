@@ -1768,6 +1768,22 @@ Tensor relu6_bwd_op(const Tensor& dy, const Tensor& gate) {
   return dx;
 }
 
+// y[n, ...] = x[n, ...] * scale[n] on a dense tensor whose samples are contiguous blocks
+// (plain-contiguous or channels_last)
+Tensor sample_scale_op(const Tensor& x, const Tensor& scale) {
+  CHECK_GPU(x); CHECK_F32(x); CHECK_GPU(scale); CHECK_F32(scale); CHECK_CONTIG(scale);
+  TORCH_CHECK(x.dim() >= 1 && scale.numel() == x.size(0),
+              "sample_scale: scale must hold one float per sample");
+  if (x.numel() == 0) return at::empty_like(x);  // an empty batch, as the CPU path returns
+  TORCH_CHECK(x.is_contiguous() ||
+                  (x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              "sample_scale: a contiguous or channels_last tensor expected");
+  auto y = at::empty_like(x);
+  sample_scale(x.data_ptr<float>(), scale.data_ptr<float>(), x.size(0), x.numel() / x.size(0),
+               y.data_ptr<float>(), cur_stream());
+  return y;
+}
+
 // x [n, ...] fp32 contiguous, y [n] int64, idx [B] int64 (all on the GPU) -> (x[idx], y[idx])
 std::vector<Tensor> gather_batch_op(const Tensor& x, const Tensor& y, const Tensor& idx,
                                     bool planes, const c10::optional<Tensor>& cursor,
@@ -2415,6 +2431,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_mask", &relu_mask_op);
   m.def("relu6_fwd", &relu6_fwd_op, py::arg("x"));
   m.def("relu6_bwd", &relu6_bwd_op, py::arg("dy"), py::arg("gate"));
+  m.def("sample_scale", &sample_scale_op, py::arg("x"), py::arg("scale"));
   // this rank's factors of a factored Linear weight into slot `rank` of the all-gather buffers:
   // g [B][out] * alpha and x [B][in]; each slot holds `slot_rows` >= B rows (the batch size the
   // ranks agreed on) and rows B.. are zeroed, so a smaller (ragged last) batch on some rank

@@ -348,6 +348,10 @@ void fill_f32(float* x, long n, float v, hipStream_t s);
 // input stays NaN. relu6_bwd: dx = gate ? dy : 0.
 void relu6_fwd(const float* x, long n, float* y, uint8_t* gate, hipStream_t s);
 void relu6_bwd(const float* dy, const uint8_t* gate, long n, float* dx, hipStream_t s);
+// y[n, ...] = x[n, ...] * scale[n]: `samples` samples of `per` consecutive elements each
+// (excite.hip; stochastic depth, forward and backward)
+void sample_scale(const float* x, const float* scale, long samples, long per, float* y,
+                  hipStream_t s);
 // 4-D strided copy over dst's logical shape; elements outside src's shape are written as 0
 // (accumulate: dst += src, and elements outside src's shape are left alone)
 struct Copy4D {

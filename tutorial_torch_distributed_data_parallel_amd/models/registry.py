@@ -32,6 +32,10 @@ def build_model(name: str, num_classes: int = 10, device=None) -> torch.nn.Modul
         from .mobilenet import mobilenet_v2
 
         return mobilenet_v2(num_classes=num_classes, device=device)
+    if name in ("efficientnet_b0", "efficientnetb0"):
+        from .efficientnet import efficientnet_b0
+
+        return efficientnet_b0(num_classes=num_classes, device=device)
     if name in ("mixer_s16", "mixer_b16"):
         from . import mixer
 

@@ -76,6 +76,13 @@ class ReLU6(nn.ReLU6):
         return ops.relu6(x)
 
 
+class SiLU(nn.SiLU):
+    """Standalone SiLU (``ops.silu``: CPU tensors; a GPU tensor raises: no kernel yet)."""
+
+    def forward(self, x):
+        return ops.silu(x)
+
+
 class MaxPool2d(nn.MaxPool2d):
     def forward(self, x):
         return ops.max_pool2d(x, self.kernel_size, self.stride, self.padding)
@@ -96,13 +103,16 @@ class _NativeBN(nn.modules.batchnorm._BatchNorm):
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
                  track_running_stats=True, relu: bool = False, device=None, dtype=None,
-                 relu6: bool = False):
+                 relu6: bool = False, silu: bool = False):
         if relu and relu6:
             raise ValueError("BatchNorm: relu and relu6 are mutually exclusive")
+        if silu and (relu or relu6):
+            raise ValueError("BatchNorm: relu, relu6 and silu are mutually exclusive")
         super().__init__(num_features, eps, momentum, affine, track_running_stats,
                          device=device, dtype=dtype)
         self.relu = relu
         self.relu6 = relu6  # fused min(max(y, 0), 6) (MobileNetV2's activation)
+        self.silu = silu  # y * sigmoid(y) (EfficientNet's activation; CPU tensors, no residual)
         self._nbt = 0  # host mirror of num_batches_tracked: no device->host sync per step
 
     def _group(self):
@@ -117,8 +127,8 @@ class _NativeBN(nn.modules.batchnorm._BatchNorm):
     def forward(self, x, residual=None, relu=None, residual_grad_into=None):
         """``act?(bn(x) [+ residual])``; ``residual`` fuses a residual join into the
         normalisation (ResNet's ``relu(bn3(conv3(.)) + identity)``, one pass instead of two).
-        ``relu`` switches the module's activation (ReLU, or ReLU6 on a ``relu6`` module) on or
-        off for this call."""
+        ``relu`` switches the module's activation (ReLU, ReLU6 on a ``relu6`` module, SiLU on a
+        ``silu`` module) on or off for this call."""
         self._check_input_dim(x)
         use_batch = self.training or not self.track_running_stats
         factor = 0.0
@@ -135,16 +145,18 @@ class _NativeBN(nn.modules.batchnorm._BatchNorm):
         # `relu` switches the module's own activation off (False) or on (True): on a relu6
         # module "on" is the ReLU6, never a silent plain ReLU
         own6 = getattr(self, "relu6", False)
-        on = (self.relu or own6) if relu is None else bool(relu)
+        own_s = getattr(self, "silu", False)
+        on = (self.relu or own6 or own_s) if relu is None else bool(relu)
         return ops.batch_norm(x, rm, rv, self.weight, self.bias, training=use_batch,
-                              momentum=factor, eps=self.eps, relu=on and not own6,
+                              momentum=factor, eps=self.eps, relu=on and not (own6 or own_s),
                               group=self._group() if use_batch else None, residual=residual,
                               num_batches_tracked=nbt, residual_grad_into=residual_grad_into,
-                              relu6=on and own6)
+                              relu6=on and own6, silu=on and own_s)
 
     def extra_repr(self) -> str:
         return super().extra_repr() + (", relu=True" if self.relu else "") + \
-            (", relu6=True" if getattr(self, "relu6", False) else "")
+            (", relu6=True" if getattr(self, "relu6", False) else "") + \
+            (", silu=True" if getattr(self, "silu", False) else "")
 
 
 class BatchNorm1d(_NativeBN):
@@ -182,7 +194,8 @@ class SyncBatchNorm(_NativeBN):
         if isinstance(module, nn.modules.batchnorm._BatchNorm) and not isinstance(module, cls):
             out = cls(module.num_features, module.eps, module.momentum, module.affine,
                       module.track_running_stats, relu=getattr(module, "relu", False),
-                      relu6=getattr(module, "relu6", False))
+                      relu6=getattr(module, "relu6", False),
+                      silu=getattr(module, "silu", False))
             if module.affine:
                 with torch.no_grad():
                     out.weight = module.weight
@@ -208,6 +221,43 @@ class LayerNorm(nn.LayerNorm):
 class GELU(nn.GELU):
     def forward(self, x):
         return ops.gelu(x, approximate=self.approximate)
+
+
+class StochasticDepth(nn.Module):
+    """torchvision's ``StochasticDepth(p, mode)`` (``ops.stochastic_depth``); ``"row"`` only."""
+
+    def __init__(self, p: float, mode: str = "row"):
+        super().__init__()
+        if mode != "row":
+            raise NotImplementedError(f"StochasticDepth: only mode='row' is supported, got "
+                                      f"{mode!r}")
+        self.p = p
+        self.mode = mode
+
+    def forward(self, x):
+        return ops.stochastic_depth(x, self.p, self.training)
+
+    def extra_repr(self) -> str:
+        return f"p={self.p}, mode={self.mode}"
+
+
+class SqueezeExcitation(nn.Module):
+    """torchvision's ``SqueezeExcitation(input_channels, squeeze_channels)`` with SiLU inside and
+    a sigmoid gate: global average pool (the NHWC kernel), ``fc1`` and ``fc2`` as 1x1 ``Conv2d``
+    with bias on the [N, C, 1, 1] map (keys ``fc1.weight [sq, C, 1, 1]``, ``fc1.bias``,
+    ``fc2.*``), the stand-alone SiLU between them, and ``ops.se_scale`` for the gate. CPU
+    tensors only so far: ``ops.silu`` and ``ops.se_scale`` have no gfx950 kernels yet and raise
+    on a GPU tensor. Fusing the squeeze into the producing BatchNorm pass is a follow-up."""
+
+    def __init__(self, input_channels: int, squeeze_channels: int, device=None):
+        super().__init__()
+        self.fc1 = Conv2d(input_channels, squeeze_channels, 1, device=device)
+        self.fc2 = Conv2d(squeeze_channels, input_channels, 1, device=device)
+
+    def forward(self, x):
+        t = ops.adaptive_avg_pool2d(x, 1)
+        t = self.fc2(ops.silu(self.fc1(t)))
+        return ops.se_scale(x, t)
 
 
 class CrossEntropyLoss(nn.CrossEntropyLoss):

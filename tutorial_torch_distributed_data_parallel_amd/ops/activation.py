@@ -9,6 +9,10 @@ fuses the one that does): on the GPU one forward kernel (csrc/elementwise.hip ``
 also writes the backward's gate as one bit per element, and one backward kernel that reads dy and
 that gate -- ``dx`` is exactly ``dy`` where ``0 < x < 6`` and exactly 0 elsewhere, both boundaries
 included (torch's ``hardtanh_backward``). A NaN input stays NaN. CPU tensors run ``F.relu6``.
+
+SiLU, ``x * sigmoid(x)`` (EfficientNet's activation): CPU tensors run ``F.silu``. Like GELU it has
+no gfx950 kernel yet -- the kernel pair written for it was withheld together with the other
+EfficientNet kernels (profiles/r19/efficientnet_b0.md) -- so a GPU tensor raises.
 """
 from __future__ import annotations
 
@@ -59,3 +63,10 @@ def relu6(x: torch.Tensor) -> torch.Tensor:
     if x.dtype != torch.float32:
         raise TypeError(f"native relu6 expects float32, got {x.dtype}")
     return _ReLU6Fn.apply(x)
+
+
+def silu(x: torch.Tensor) -> torch.Tensor:
+    """``F.silu(x)``."""
+    if x.is_cuda:
+        raise NotImplementedError("silu has no native gfx950 kernel yet (CPU tensors only)")
+    return F.silu(x)

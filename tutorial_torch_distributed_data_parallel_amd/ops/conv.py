@@ -406,7 +406,14 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     torch's ``[Cout, Cin/groups, R, S]``); ``grouped_family`` states which channel counts are
     taken, any other raises ``NotImplementedError``. ``bn_stats`` produces nothing there -- except,
     with ``DW_BN_STATS``, for a 3x3 / 5x5 depthwise convolution with channel multiplier 1, no bias
-    and no ReLU -- and the convolution stays fp32 inside ``tdp.autocast``. ``dilation`` other than 1 is not supported."""
+    and no ReLU -- and the convolution stays fp32 inside ``tdp.autocast``. ``dilation`` other than 1 is not supported.
+
+    Squeeze-and-excitation (``nn.SqueezeExcitation``) runs its two 1x1 convolutions WITH bias on
+    [N, C, 1, 1] maps through this function: N-row problems. EfficientNet-B0's squeeze widths 8, 4,
+    20, 28 and 48 take the NHWC path, 6 and 10 (no multiples of 4) the NCHW fallback kernels.
+    The module as a whole runs on CPU tensors only so far (its SiLU and gate have no kernels).
+    The 4-row NHWC backward with bias (32 -> 8 -> 32) is the suspected, unproven site of the
+    fault recorded in profiles/r19/efficientnet_b0.md: read it before relying on that shape."""
     stride, padding = _pair(stride), _pair(padding)
     if _pair(dilation) != (1, 1):
         raise NotImplementedError("conv2d: dilation is not supported (dilation must be 1)")

@@ -22,6 +22,15 @@ zero gradient at both boundaries as in torch's ``hardtanh_backward``). The 1-byt
 mask of the [rows, C % 4 == 0] form stores that gate, so the mask-reading backward kernels serve
 both; the forms that re-read the saved float output are told the kind (``act=``).
 
+Kind 3 is SiLU (``silu=True``, EfficientNet's activation), on CPU tensors only so far: the torch
+kernels (``_TorchKernels``) apply ``F.silu`` in the normalisation and, since SiLU is smooth and
+fits no mask, recompute ``z = (x - mean) * rstd * w + b`` from the saved input, statistics and
+affine pair in both backward halves and use ``dy * silu'(z)`` where the other kinds use the
+masked ``dy`` -- no new saved tensor, and nothing further under SyncBatchNorm (the gloo path).
+The gfx950 kernels have no kind 3 yet (withheld: profiles/r19/efficientnet_b0.md), so
+``silu=True`` on a GPU tensor raises ``NotImplementedError``. ``silu`` with ``residual=`` is a
+``ValueError`` (no network here needs it), and ``silu`` excludes ``relu`` / ``relu6``.
+
 Reference: the README's SyncBatchNorm pitfall (/root/reference/README.md:79-81) -- BatchNorm
 statistics must be synced across ranks, via ``convert_sync_batchnorm`` before wrapping in DDP.
 """
@@ -32,15 +41,20 @@ import torch
 import torch.nn.functional as F
 
 from .._native import native
+from .activation import silu as _silu_op  # (batch_norm has a parameter named silu)
 from ._grad import bias_epilogue, grad_dest, hand_off, needs
 from .linear import attach_planes, planes_input_fit
 
 
-_RELU6 = 2  # the kernels' activation kind: 0 none, 1 (True) ReLU, 2 ReLU6
+_RELU6 = 2  # the kernels' activation kind: 0 none, 1 (True) ReLU, 2 ReLU6, 3 SiLU
+_SILU = 3
 
 
 def _act(y, kind):
-    """The fused activation ``kind`` in torch ops."""
+    """The fused activation ``kind`` in torch ops (SiLU: ``ops.silu``, which takes CPU tensors
+    only)."""
+    if kind == _SILU:
+        return _silu_op(y)
     if kind == _RELU6:
         return F.relu6(y)
     return F.relu(y) if kind else y
@@ -49,6 +63,11 @@ def _act(y, kind):
 def _gate(y, kind):
     """Where the activation that produced ``y`` has slope 1."""
     return (y > 0) & (y < 6) if kind == _RELU6 else (y > 0)
+
+
+def _silu_grad(z):
+    s = torch.sigmoid(z)
+    return s * (1 + z * (1 - s))
 
 
 class _TorchKernels:
@@ -95,9 +114,11 @@ class _TorchKernels:
             y = y + residual
         return _act(y, relu)
 
-    def bn_bwd_reduce(self, dy, x, stats, y, dw, db, beta, act=1):
+    def bn_bwd_reduce(self, dy, x, stats, y, dw, db, beta, act=1, w=None, b=None):
         C = x.shape[1]
-        if y is not None:
+        if act == _SILU:  # recomputed from the saved operands: no mask, no saved output
+            dy = dy * _silu_grad(self.bn_elemt(x, stats, w, b, 0))
+        elif y is not None:
             dy = dy * _gate(y, act)
         dv, xv = self._view(dy), self._view(x)
         s_dy = dv.sum(dim=(0, 2))
@@ -108,10 +129,12 @@ class _TorchKernels:
             db.copy_(s_dy)
         return torch.cat([s_dy, s_dyx])
 
-    def bn_bwd_elemt(self, dy, x, stats, w, sums, y, residual_grad=False, act=1):
+    def bn_bwd_elemt(self, dy, x, stats, w, sums, y, residual_grad=False, act=1, b=None):
         C = x.shape[1]
         shape = (1, C) + (1,) * (x.dim() - 2)
-        if y is not None:
+        if act == _SILU:
+            dy = dy * _silu_grad(self.bn_elemt(x, stats, w, b, 0))
+        elif y is not None:
             dy = dy * _gate(y, act)
         cnt = stats[2 * C]
         inv = stats[C: 2 * C].view(shape)
@@ -187,7 +210,7 @@ class _BatchNormFn(torch.autograd.Function):
         # instead of the float output (1/16 of the bytes, twice per backward)
         mask = None
         rows4 = x.is_cuda and x.dim() == 2 and C % 4 == 0
-        if relu and rows4:
+        if relu and relu != _SILU and rows4:
             mask = torch.empty((x.shape[0], C // 4), dtype=torch.uint8, device=x.device)
         # a BatchNorm1d output feeding a skinny Linear: its bf16 split planes from the same pass
         pl = None
@@ -259,7 +282,9 @@ class _BatchNormFn(torch.autograd.Function):
         ctx.group = group
         ctx.has_res = residual is not None
         ctx.sink = sink
-        ctx.save_for_backward(x, weight, stats, y if (relu and mask is None) else None, mask)
+        # (SiLU saves neither: its backward recomputes the pre-activation from x, stats, w, b)
+        ctx.save_for_backward(x, weight, stats,
+                              y if (relu and relu != _SILU and mask is None) else None, mask)
         return _unrows(y, ctx.shape4) if ctx.nhwc else y
 
     @staticmethod
@@ -274,6 +299,9 @@ class _BatchNormFn(torch.autograd.Function):
         mk = {} if mask is None else {"mask": mask}
         if ctx.relu == _RELU6 and y is not None:
             mk["act"] = _RELU6  # the saved float output is gated on 0 < y < 6
+        if ctx.relu == _SILU:
+            mk["act"] = _SILU  # dy * silu'(z), z recomputed from x, stats and the affine pair
+            mk["b"] = b_param
         if ctx.local1d and ctx.group is None:
             # one launch: the column sums, dw / db and dx (+ its planes) of a whole-rows batch
             pl = None
@@ -312,7 +340,8 @@ class _BatchNormFn(torch.autograd.Function):
             if sums is not None and sums.numel() == 0:
                 sums = None
         if sums is None:
-            sums = K.bn_bwd_reduce(dy, x, stats, y, dw, db, 0.0, **mk)
+            rk = dict(mk, w=weight) if ctx.relu == _SILU else mk
+            sums = K.bn_bwd_reduce(dy, x, stats, y, dw, db, 0.0, **rk)
         dx = dres = None
         want_res = ctx.has_res and needs(ctx, 9)
         if needs(ctx, 0) or want_res:
@@ -352,12 +381,22 @@ def batch_norm(x: torch.Tensor, running_mean: torch.Tensor | None,
                bias: torch.Tensor | None = None, training: bool = True, momentum: float = 0.1,
                eps: float = 1e-5, relu: bool = False, group=None, residual=None,
                num_batches_tracked=None, residual_grad_into=None,
-               relu6: bool = False) -> torch.Tensor:
+               relu6: bool = False, silu: bool = False) -> torch.Tensor:
     """``act?(batch_norm(x) [+ residual])`` over dim 1 of x ([N, C] or [N, C, *]) with ``act`` a
-    ReLU (``relu``) or a ReLU6 (``relu6``; not both); ``group`` makes it synchronous;
+    ReLU (``relu``), a ReLU6 (``relu6``) or a SiLU (``silu``; at most one of the three, and no
+    ``silu`` with a ``residual``); ``group`` makes it synchronous;
     ``num_batches_tracked`` (training) is incremented on the device; ``residual_grad_into`` (a
     ``SharedGrad``) receives the residual's gradient."""
-    if relu6:
+    if silu:
+        if relu or relu6:
+            raise ValueError("batch_norm: relu, relu6 and silu are mutually exclusive")
+        if residual is not None:
+            raise ValueError("batch_norm: silu cannot be combined with a fused residual")
+        if x.is_cuda:
+            raise NotImplementedError("batch_norm: silu has no native gfx950 kernel yet (CPU "
+                                      "tensors only)")
+        relu = _SILU
+    elif relu6:
         if relu:
             raise ValueError("batch_norm: relu and relu6 are mutually exclusive")
         relu = _RELU6  # the kernels' third activation kind; bool(relu) otherwise, as before

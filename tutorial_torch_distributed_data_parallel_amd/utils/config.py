@@ -15,7 +15,7 @@ import yaml
 
 TRAIN_DEFAULTS = {
     "model": "alexnet",          # alexnet | toy_mlp | toy_mlp_syncbn | resnet50 | resnext50_32x4d |
-                                 # mixer_s16 | mixer_b16 | mobilenet_v2
+                                 # mixer_s16 | mixer_b16 | mobilenet_v2 | efficientnet_b0
     "train_batch_size": 128,     # REF/multi-GPU-training-torch.py:88
     "test_batch_size": 100,      # :95
     "num_epochs": 20,            # :166
