@@ -1237,6 +1237,99 @@ std::vector<Tensor> bn_bwd_elemt_op(const Tensor& dy, const Tensor& x, const Ten
   return {dx};
 }
 
+// ----------------------------------------------------------------------------------- group norm
+// `x` in its memory form: NHWC form [N, HW, C] (the channels_last tensor's pixel rows), generic
+// form [N, C, *]; both contiguous. Results come back in the same form.
+struct GnDims {
+  int N, C, HW;
+};
+
+static GnDims gn_dims(const Tensor& x, int64_t G, bool nhwc, const char* op) {
+  CHECK_GPU(x); CHECK_F32(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.dim() >= 2, op, ": input must be at least 2-D");
+  TORCH_CHECK(!nhwc || x.dim() == 3, op, ": the NHWC form takes [N, HW, C]");
+  TORCH_CHECK(x.numel() > 0, op, ": empty input");
+  GnDims d;
+  d.N = (int)x.size(0);
+  d.C = (int)(nhwc ? x.size(2) : x.size(1));
+  d.HW = (int)(x.numel() / ((int64_t)d.N * d.C));
+  TORCH_CHECK(x.size(0) < (1L << 31) && x.numel() / x.size(0) < (1L << 31), op,
+              ": a sample must have < 2^31 elements");
+  TORCH_CHECK(G >= 1 && d.C % G == 0, op, ": ", d.C, " channels are not divisible into ", G,
+              " groups");
+  TORCH_CHECK(!nhwc || (d.C % 4 == 0 && ((uintptr_t)x.data_ptr() & 15) == 0), op,
+              ": the NHWC form needs C % 4 == 0 and a 16-byte aligned tensor");
+  return d;
+}
+
+static const float* gn_like(const c10::optional<Tensor>& t, const Tensor& x, bool nhwc,
+                            const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                  t->sizes() == x.sizes(), what, " must be a contiguous float32 GPU tensor of "
+              "the input's shape");
+  TORCH_CHECK(!nhwc || ((uintptr_t)t->data_ptr() & 15) == 0, what, " must be 16-byte aligned");
+  return t->data_ptr<float>();
+}
+
+// -> [y, stats [mean(N*G) | rstd(N*G)]] (+ [mask] when want_mask: NHWC form with relu)
+std::vector<Tensor> gn_fwd_op(const Tensor& x, int64_t G, const c10::optional<Tensor>& w,
+                              const c10::optional<Tensor>& b, double eps, bool relu,
+                              const c10::optional<Tensor>& residual, bool nhwc, bool want_mask) {
+  const GnDims d = gn_dims(x, G, nhwc, "gn_fwd");
+  const float* wp = opt_vec(w, d.C, "gn_fwd: weight");
+  const float* bp = opt_vec(b, d.C, "gn_fwd: bias");
+  const float* rp = gn_like(residual, x, nhwc, "gn_fwd: residual");
+  TORCH_CHECK(!want_mask || (nhwc && relu), "gn_fwd: the ReLU mask exists in the NHWC form");
+  auto y = at::empty_like(x);
+  auto stats = at::empty({2 * (int64_t)d.N * G}, x.options());
+  auto ws = at::empty({gn_ws_floats(d.N, d.C, d.HW, (int)G, nhwc)}, x.options());
+  Tensor mask;
+  if (want_mask) mask = at::empty({x.numel() / 4}, x.options().dtype(at::kByte));
+  gn_fwd(x.data_ptr<float>(), wp, bp, rp, d.N, d.C, d.HW, (int)G, nhwc, (float)eps, relu ? 1 : 0,
+         ws.data_ptr<float>(), stats.data_ptr<float>(), y.data_ptr<float>(),
+         want_mask ? mask.data_ptr<uint8_t>() : nullptr, cur_stream());
+  if (want_mask) return {y, stats, mask};
+  return {y, stats};
+}
+
+// -> [dx, dres, dw, db]; an output not asked for is an undefined tensor (None). dw / db, when
+// given, are written in place (the parameter's gradient slot) and returned.
+std::vector<c10::optional<Tensor>> gn_bwd_op(
+    const Tensor& dy, const Tensor& x, const Tensor& stats, int64_t G,
+    const c10::optional<Tensor>& w, const c10::optional<Tensor>& y_relu,
+    const c10::optional<Tensor>& mask, bool nhwc, bool want_dx, bool want_dres,
+    const c10::optional<Tensor>& dw, const c10::optional<Tensor>& db) {
+  const GnDims d = gn_dims(x, G, nhwc, "gn_bwd");
+  const float* dyp = gn_like(dy, x, nhwc, "gn_bwd: dy");
+  const float* yp = gn_like(y_relu, x, nhwc, "gn_bwd: y_relu");
+  const float* wp = opt_vec(w, d.C, "gn_bwd: weight");
+  float* dwp = opt_vec(dw, d.C, "gn_bwd: dw");
+  float* dbp = opt_vec(db, d.C, "gn_bwd: db");
+  const float* sp = opt_vec(stats, 2 * (int64_t)d.N * G, "gn_bwd: stats");
+  const uint8_t* mp = nullptr;
+  if (mask.has_value() && mask->defined()) {
+    TORCH_CHECK(nhwc && mask->is_cuda() && mask->scalar_type() == at::kByte &&
+                    mask->is_contiguous() && mask->numel() == x.numel() / 4,
+                "gn_bwd: the ReLU mask is numel / 4 bytes of the NHWC form");
+    mp = mask->data_ptr<uint8_t>();
+  }
+  TORCH_CHECK(!(nhwc && yp), "gn_bwd: the NHWC form reads the ReLU mask, not the output");
+  Tensor dx, dres;
+  if (want_dx) dx = at::empty_like(x);
+  if (want_dres) dres = at::empty_like(x);
+  auto ws = at::empty({gn_ws_floats(d.N, d.C, d.HW, (int)G, nhwc)}, x.options());
+  auto ab = at::empty({2 * (int64_t)d.N * d.C + 2 * (int64_t)d.N * G}, x.options());
+  gn_bwd(dyp, x.data_ptr<float>(), sp, wp, yp, mp, d.N, d.C, d.HW, (int)G, nhwc,
+         ws.data_ptr<float>(), ab.data_ptr<float>(), ab.data_ptr<float>() + 2L * d.N * d.C,
+         want_dx ? dx.data_ptr<float>() : nullptr, want_dres ? dres.data_ptr<float>() : nullptr,
+         dwp, dbp, cur_stream());
+  auto opt = [](const Tensor& t) {
+    return t.defined() ? c10::optional<Tensor>(t) : c10::optional<Tensor>();
+  };
+  return {opt(dx), opt(dres), dw, db};
+}
+
 // ---------------------------------------------------------------------------------- conv / pool
 ConvGeom conv_geom(const std::vector<int64_t>& xs, const std::vector<int64_t>& ws,
                    int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
@@ -2518,6 +2611,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_elemt", &bn_bwd_elemt_op, py::arg("dy"), py::arg("x"), py::arg("stats"),
         py::arg("w"), py::arg("sums"), py::arg("y_relu"), py::arg("residual_grad") = false,
         py::arg("mask") = py::none(), py::arg("planes_out") = py::none(), py::arg("act") = 1);
+
+  m.def("gn_fwd", &gn_fwd_op, py::arg("x"), py::arg("groups"), py::arg("w"), py::arg("b"),
+        py::arg("eps"), py::arg("relu") = false, py::arg("residual") = py::none(),
+        py::arg("nhwc") = false, py::arg("want_mask") = false);
+  m.def("gn_bwd", &gn_bwd_op, py::arg("dy"), py::arg("x"), py::arg("stats"), py::arg("groups"),
+        py::arg("w"), py::arg("y_relu") = py::none(), py::arg("mask") = py::none(),
+        py::arg("nhwc") = false, py::arg("want_dx") = true, py::arg("want_dres") = false,
+        py::arg("dw") = py::none(), py::arg("db") = py::none());
 
   m.def("rccl_unique_id", &unique_id_op);
   m.def("debug_spin_ms", [](int ms) { debug_spin_ms(ms, cur_stream()); });

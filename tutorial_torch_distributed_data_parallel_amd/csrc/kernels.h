@@ -465,4 +465,28 @@ bool bn1d_local_bwd(const float* dy, const float* x, const float* stats, const f
                     uint16_t* planes_out, hipStream_t s, const OptEpilogue* wopt = nullptr,
                     const OptEpilogue* bopt = nullptr);
 
+// ------------------------------------------------------------------------------------------------
+// Group norm (csrc/groupnorm.hip). x is [N][C][HW], G groups of C / G channels, statistics per
+// (sample, group) over its (C / G) * HW elements. `nhwc`: channels_last [N][HW][C] with
+// C % 4 == 0 and 16-byte aligned tensors (a thread owns 4 channels); otherwise any contiguous
+// [N][C][HW] (scalar loads, any alignment). No atomics; the reduction partition of a sample
+// depends on (C, HW, G) only, so results are reproducible and independent of the batch around a
+// sample.
+// ------------------------------------------------------------------------------------------------
+int gn_parts(int C, int HW, int G, bool nhwc);
+long gn_ws_floats(int N, int C, int HW, int G, bool nhwc);  // `ws` of gn_fwd and of gn_bwd
+// stats [mean(N*G) | rstd(N*G)] out; y = act((x - mean) * rstd * w + b [+ residual]), act = ReLU
+// when relu. w / b / residual may be null. mask_out (NHWC form with relu, else null): the ReLU
+// gate as one byte per 4 channels (BatchNorm's mask format).
+void gn_fwd(const float* x, const float* w, const float* b, const float* residual, int N, int C,
+            int HW, int G, bool nhwc, float eps, int relu, float* ws, float* stats, float* y,
+            uint8_t* mask_out, hipStream_t s);
+// g = dy gated by the ReLU: `mask` (NHWC form) or the saved output `y_relu` (generic form), both
+// null without a ReLU. ab [N][2][C] (per-sample sum g | sum g xhat) and gs [N*G][2] are scratch.
+// dx, dres (= g, the fused residual's gradient), dw, db are each optional.
+void gn_bwd(const float* dy, const float* x, const float* stats, const float* w,
+            const float* y_relu, const uint8_t* mask, int N, int C, int HW, int G, bool nhwc,
+            float* ws, float* ab, float* gs, float* dx, float* dres, float* dw, float* db,
+            hipStream_t s);
+
 }  // namespace tdp

@@ -21,44 +21,10 @@
 #include "kernels.h"
 #include "optim_elem.h"
 #include "split_bf16.h"
+#include "welford.h"  // Wf, wf_merge, wf_push, wf_wave (shared with groupnorm.hip)
 
 namespace tdp {
 namespace {
-
-struct Wf {
-  float n, mean, m2;
-};
-
-__device__ __forceinline__ Wf wf_merge(Wf a, Wf b) {
-  const float n = a.n + b.n;
-  if (n == 0.f) return a;
-  const float d = b.mean - a.mean;
-  const float fb = b.n / n;
-  Wf r;
-  r.n = n;
-  r.mean = fmaf(d, fb, a.mean);
-  r.m2 = a.m2 + b.m2 + d * d * a.n * fb;
-  return r;
-}
-
-__device__ __forceinline__ void wf_push(Wf& w, float x) {
-  w.n += 1.f;
-  const float d = x - w.mean;
-  w.mean = fmaf(d, 1.f / w.n, w.mean);
-  w.m2 = fmaf(d, x - w.mean, w.m2);
-}
-
-__device__ __forceinline__ Wf wf_wave(Wf w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    Wf t;
-    t.n = __shfl_xor(w.n, o, 64);
-    t.mean = __shfl_xor(w.mean, o, 64);
-    t.m2 = __shfl_xor(w.m2, o, 64);
-    w = wf_merge(w, t);
-  }
-  return w;
-}
 
 __device__ __forceinline__ void range_of(long total, int splits, int z, long& b, long& e) {
   const long per = (total + splits - 1) / splits;

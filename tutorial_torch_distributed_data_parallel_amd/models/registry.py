@@ -24,6 +24,10 @@ def build_model(name: str, num_classes: int = 10, device=None) -> torch.nn.Modul
         from .resnet import resnet50
 
         return resnet50(num_classes=num_classes, device=device)
+    if name in ("resnet50_gn", "resnet-50-gn"):
+        from .resnet import resnet50_gn
+
+        return resnet50_gn(num_classes=num_classes, device=device)
     if name == "resnext50_32x4d":
         from .resnet import resnext50_32x4d
 

@@ -8,6 +8,12 @@ tensors -- many small gradients, which is what stresses the bucketed all-reduce 
 §2.6). ReLU is fused into the batch-norm kernels (``relu=True``) and the residual join
 ``relu(bn3(conv3) + identity)`` is fused into bn3's normalisation pass (and its backward). ``convert_sync_batchnorm`` turns the BatchNorm2d layers into SyncBatchNorm.
 Weights use torchvision's initialisation (Kaiming-normal fan_out convs, BN gamma=1 beta=0).
+
+``norm_layer`` (``Bottleneck`` and ``ResNet``) swaps the normalisation: a callable
+``(channels, relu=False, device=None) -> module``; the default builds today's ``BatchNorm2d``.
+``resnet50_gn`` uses ``GroupNorm(32, channels)`` (csrc/groupnorm.hip) -- the network
+``torchvision.models.resnet50(norm_layer=lambda c: nn.GroupNorm(32, c))`` builds, with the same
+attribute names (``bn1`` ...), no buffers, and no batch statistics asked of the convolutions.
 """
 from __future__ import annotations
 
@@ -16,24 +22,29 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops._grad import SharedGrad, fork
-from ..nn import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Linear, MaxPool2d
+from ..nn import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, GroupNorm, Linear, MaxPool2d
+
+
+def _batch_norm(channels, relu=False, device=None):
+    return BatchNorm2d(channels, relu=relu, device=device)
 
 
 class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, device=None, groups=1,
-                 base_width=64):
+                 base_width=64, norm_layer=None):
         super().__init__()
+        norm_layer = norm_layer or _batch_norm
         kw = dict(bias=False, device=device)
         # torchvision's width rule: ResNeXt widens the 3x3 and splits it into groups
         width = int(planes * base_width / 64) * groups
         self.conv1 = Conv2d(inplanes, width, 1, **kw)
-        self.bn1 = BatchNorm2d(width, relu=True, device=device)
+        self.bn1 = norm_layer(width, relu=True, device=device)
         self.conv2 = Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, **kw)
-        self.bn2 = BatchNorm2d(width, relu=True, device=device)
+        self.bn2 = norm_layer(width, relu=True, device=device)
         self.conv3 = Conv2d(width, planes * 4, 1, **kw)
-        self.bn3 = BatchNorm2d(planes * 4, device=device)
+        self.bn3 = norm_layer(planes * 4, device=device)
         self.downsample = downsample
         self.stride = stride
         self._fused_join = True
@@ -77,12 +88,13 @@ def _takes_sink(m) -> bool:
 
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes: int = 10, device=None, groups=1,
-                 width_per_group=64):
+                 width_per_group=64, norm_layer=None):
         super().__init__()
+        self._norm_layer = norm_layer or _batch_norm
         self.inplanes = 64
         self.groups, self.base_width = groups, width_per_group
         self.conv1 = Conv2d(3, 64, 7, stride=2, padding=3, bias=False, device=device)
-        self.bn1 = BatchNorm2d(64, relu=True, device=device)
+        self.bn1 = self._norm_layer(64, relu=True, device=device)
         self.maxpool = MaxPool2d(kernel_size=3, stride=2, padding=1)
         self.layer1 = self._make_layer(64, layers[0], 1, device)
         self.layer2 = self._make_layer(128, layers[1], 2, device)
@@ -91,27 +103,36 @@ class ResNet(nn.Module):
         self.avgpool = AdaptiveAvgPool2d((1, 1))
         self.fc = Linear(512 * Bottleneck.expansion, num_classes, device=device)
         # every convolution here feeds a BatchNorm: its GEMM epilogue emits the statistics
-        self.conv1.bn_stats = True
-        for m in self.modules():
-            if isinstance(m, Bottleneck):
-                for c in (m.conv1, m.conv2, m.conv3):
-                    c.bn_stats = True
-                if m.downsample is not None and isinstance(m.downsample[0], Conv2d):
-                    m.downsample[0].bn_stats = True
+        # (per-channel batch statistics are of no use to another normalisation)
+        for conv, norm in self._conv_norm_pairs():
+            if isinstance(norm, nn.modules.batchnorm._BatchNorm):
+                conv.bn_stats = True
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
+        del self._norm_layer  # construction only (a closure would not pickle with the model)
+
+    def _conv_norm_pairs(self):
+        yield self.conv1, self.bn1
+        for m in self.modules():
+            if isinstance(m, Bottleneck):
+                yield m.conv1, m.bn1
+                yield m.conv2, m.bn2
+                yield m.conv3, m.bn3
+                if m.downsample is not None and isinstance(m.downsample[0], Conv2d):
+                    yield m.downsample[0], m.downsample[1]
 
     def _make_layer(self, planes, blocks, stride, device):
         downsample = None
         if stride != 1 or self.inplanes != planes * Bottleneck.expansion:
             downsample = nn.Sequential(
                 Conv2d(self.inplanes, planes * 4, 1, stride=stride, bias=False, device=device),
-                BatchNorm2d(planes * 4, device=device))
-        kw = dict(device=device, groups=self.groups, base_width=self.base_width)
+                self._norm_layer(planes * 4, device=device))
+        kw = dict(device=device, groups=self.groups, base_width=self.base_width,
+                  norm_layer=self._norm_layer)
         layers = [Bottleneck(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * 4
         for _ in range(1, blocks):
@@ -134,3 +155,13 @@ def resnext50_32x4d(num_classes: int = 10, device=None) -> ResNet:
     32-group 3x3 of 4 channels per group at layer1, doubling per stage."""
     return ResNet((3, 4, 6, 3), num_classes=num_classes, device=device, groups=32,
                   width_per_group=4)
+
+
+def resnet50_gn(num_classes: int = 10, device=None, groups: int = 32) -> ResNet:
+    """ResNet-50 with ``GroupNorm(groups, channels)`` in place of every BatchNorm (weight 1,
+    bias 0, no buffers): per-sample statistics, so no SyncBatchNorm conversion is needed under
+    data parallelism."""
+    def norm(channels, relu=False, device=None):
+        return GroupNorm(groups, channels, relu=relu, device=device)
+
+    return ResNet((3, 4, 6, 3), num_classes=num_classes, device=device, norm_layer=norm)

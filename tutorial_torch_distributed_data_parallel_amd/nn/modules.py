@@ -210,6 +210,34 @@ class SyncBatchNorm(_NativeBN):
         return out
 
 
+class GroupNorm(nn.GroupNorm):
+    """``nn.GroupNorm`` on the native kernels (``ops.group_norm``), with an optional fused ReLU
+    (``relu=True``) and residual join. Per-sample statistics: no collective under data
+    parallelism and nothing for ``convert_sync_batchnorm`` to convert; training and eval are the
+    same computation. ``state_dict`` keys, init and ``extra_repr`` are torch's."""
+
+    def __init__(self, num_groups: int, num_channels: int, eps: float = 1e-5,
+                 affine: bool = True, relu: bool = False, device=None, dtype=None):
+        super().__init__(num_groups, num_channels, eps=eps, affine=affine, device=device,
+                         dtype=dtype)
+        self.relu = relu
+
+    def relu_join(self, x, residual, grad_into=None):
+        """``relu(gn(x) + residual)`` as one normalisation pass (ResNet's residual join);
+        ``grad_into``: the residual's gradient goes into that ``SharedGrad``."""
+        return self.forward(x, residual, relu=True, residual_grad_into=grad_into)
+
+    def forward(self, x, residual=None, relu=None, residual_grad_into=None):
+        """``relu?(gn(x) [+ residual])``; ``relu`` overrides the module's own setting for this
+        call."""
+        on = self.relu if relu is None else bool(relu)
+        return ops.group_norm(x, self.num_groups, self.weight, self.bias, self.eps, relu=on,
+                              residual=residual, residual_grad_into=residual_grad_into)
+
+    def extra_repr(self) -> str:
+        return super().extra_repr() + (", relu=True" if self.relu else "")
+
+
 class LayerNorm(nn.LayerNorm):
     """``nn.LayerNorm`` through ``ops.layer_norm`` (CPU tensors; a GPU tensor raises: no kernel
     yet)."""
