@@ -2147,6 +2147,57 @@ Tensor image_transform_op(const Tensor& x, const c10::optional<Tensor>& flip, in
   return out;
 }
 
+// uint8 NHWC batch + per-sample boxes (device int32 [B,4]: top, left, h, w) -> cropped, antialias-
+// resized, flipped, normalised float [B, C, Ho, Wo]. check_boxes reads the boxes back (one sync)
+// to reject h, w < 1; a caller that validated them on the host before the upload passes false.
+Tensor image_crop_resize_op(const Tensor& x, const Tensor& box, const c10::optional<Tensor>& flip,
+                            int64_t Ho, int64_t Wo, std::vector<double> mean,
+                            std::vector<double> stdv, bool round_u8, bool channels_last,
+                            double fill, bool check_boxes) {
+  CHECK_GPU(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.scalar_type() == at::kByte && x.dim() == 4, "image_crop_resize: uint8 [B,H,W,C]");
+  const int B = (int)x.size(0), Hs = (int)x.size(1), Ws = (int)x.size(2), C = (int)x.size(3);
+  TORCH_CHECK(C == 1 || C == 3 || C == 4, "image_crop_resize: 1, 3 or 4 channels");
+  TORCH_CHECK((int)mean.size() == C && (int)stdv.size() == C, "image_crop_resize: mean/std size");
+  TORCH_CHECK(x.size(0) <= 65535, "image_crop_resize: at most 65535 samples per call");
+  TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= kCropMaxExtent && Wo <= kCropMaxExtent,
+              "image_crop_resize: output size out of range");
+  TORCH_CHECK(fill >= 0.0 && fill <= 255.0, "image_crop_resize: fill must be in [0, 255]");
+  CHECK_GPU(box); CHECK_CONTIG(box);
+  TORCH_CHECK(box.device() == x.device(), "image_crop_resize: box and x on different devices");
+  TORCH_CHECK(box.scalar_type() == at::kInt && box.dim() == 2 && box.size(0) == B &&
+                  box.size(1) == 4, "image_crop_resize: box must be int32 [B, 4] (top, left, h, w)");
+  if (check_boxes && B > 0) {
+    const Tensor hb = box.cpu();
+    const int* p = hb.data_ptr<int>();
+    for (int b = 0; b < B; ++b) {
+      TORCH_CHECK(p[4 * b + 2] >= 1 && p[4 * b + 3] >= 1 && p[4 * b + 2] <= kCropMaxExtent &&
+                      p[4 * b + 3] <= kCropMaxExtent,
+                  "image_crop_resize: box ", b, " has h, w = ", p[4 * b + 2], ", ", p[4 * b + 3],
+                  " (need 1 <= h, w <= ", kCropMaxExtent, ")");
+    }
+  }
+  const uint8_t* fl = nullptr;
+  if (flip.has_value() && flip->defined()) {
+    CHECK_GPU(*flip); CHECK_CONTIG(*flip);
+    TORCH_CHECK(flip->scalar_type() == at::kByte && flip->numel() == B, "flip: uint8 [B]");
+    fl = flip->data_ptr<uint8_t>();
+  }
+  ImageNorm nrm{};
+  for (int c = 0; c < C; ++c) {
+    nrm.mean[c] = (float)mean[c];
+    nrm.inv_std[c] = (float)(1.0 / stdv[c]);
+  }
+  auto opts = x.options().dtype(at::kFloat);
+  Tensor out = channels_last
+                   ? at::empty({B, C, Ho, Wo}, opts.memory_format(at::MemoryFormat::ChannelsLast))
+                   : at::empty({B, C, Ho, Wo}, opts);
+  image_crop_resize(x.data_ptr<uint8_t>(), box.data_ptr<int>(), fl, out.data_ptr<float>(), B, Hs,
+                    Ws, C, (int)Ho, (int)Wo, (float)fill, nrm, round_u8, channels_last,
+                    cur_stream());
+  return out;
+}
+
 // the native prefetcher plus the tensors whose memory it reads
 struct PyHostLoader {
   Tensor data, labels;
@@ -2565,6 +2616,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("image_transform", &image_transform_op, py::arg("x"), py::arg("flip"), py::arg("Ho"),
         py::arg("Wo"), py::arg("mean"), py::arg("std"), py::arg("round_u8") = true,
         py::arg("channels_last") = true);
+  m.def("image_crop_resize", &image_crop_resize_op, py::arg("x"), py::arg("box"), py::arg("flip"),
+        py::arg("Ho"), py::arg("Wo"), py::arg("mean"), py::arg("std"), py::arg("round_u8") = true,
+        py::arg("channels_last") = true, py::arg("fill") = 0.0, py::arg("check_boxes") = true);
+  m.attr("CROP_TILE") = kCropTile;
+  m.attr("CROP_STAGE_ROWS") = kCropStageRows;
   py::class_<PyHostLoader, std::shared_ptr<PyHostLoader>>(m, "HostBatchLoader")
       .def(py::init(&make_host_loader), py::arg("data"), py::arg("labels"), py::arg("batch"),
            py::arg("depth") = 4, py::arg("threads") = 2, py::arg("pinned") = true)

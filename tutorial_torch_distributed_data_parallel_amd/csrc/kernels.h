@@ -376,6 +376,16 @@ struct ImageNorm {
 void image_transform(const uint8_t* x, const uint8_t* flip, float* out, int B, int Hs, int Ws,
                      int C, int Ho, int Wo, const ImageNorm& nrm, bool round_u8,
                      bool channels_last, hipStream_t s);
+// Crop + antialiased resize (csrc/image_crop.hip): sample b's box = (top, left, h, w) in source
+// pixels (int32 [B][4] on the device; it may hang over the image, `fill` outside), resized to
+// Ho x Wo with the triangle filter of support max(scale, 1) clipped at the box, then rounding /
+// flip / normalisation and the output layouts of image_transform. C in {1, 3, 4}, B <= 65535.
+constexpr int kCropTile = 16;            // output tile edge of one workgroup
+constexpr int kCropStageRows = 64;       // source rows of the horizontal pass held in LDS at once
+constexpr int kCropMaxExtent = 1 << 23;  // largest box / output extent (integer weights < 2^24)
+void image_crop_resize(const uint8_t* x, const int* box, const uint8_t* flip, float* out, int B,
+                       int Hs, int Ws, int C, int Ho, int Wo, float fill, const ImageNorm& nrm,
+                       bool round_u8, bool channels_last, hipStream_t s);
 void bf16_to_f32_copy(const uint16_t* x, float* y, long n, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------

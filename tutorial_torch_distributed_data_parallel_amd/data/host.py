@@ -16,6 +16,10 @@ Here:
     reference's float batch) on the current stream, then ``image_transform`` (csrc/image.hip)
     does resize + flip + /255 + normalise in one pass on the GPU and writes the channels_last
     float batch the convolutions consume.
+  * ``CropTransform`` is the training-recipe variant: per-sample boxes (RandomResizedCrop,
+    RandomCrop(padding) or a centre crop) drawn on the host, uploaded through a pinned buffer,
+    and ``image_crop_resize`` (csrc/image_crop.hip) crops, resizes with the antialiased
+    triangle filter, flips and normalises in one launch.
 On CPU the same classes run the torch reference implementation of the transform (the oracle of
 the tests). Parity with torchvision/PIL itself is unpinned here (neither is importable): the
 kernel implements PIL's upsampling filter (bilinear, half-pixel centres) with PIL-style rounding
@@ -161,6 +165,157 @@ class ImageTransform:
         return y.contiguous(memory_format=torch.channels_last) if self.channels_last else y
 
 
+def _norm_size(size):
+    return (size, size) if isinstance(size, int) else tuple(size)
+
+
+def _check_boxes(boxes: torch.Tensor, n: int) -> None:
+    if boxes.dtype != torch.int32 or boxes.dim() != 2 or tuple(boxes.shape) != (n, 4):
+        raise ValueError(f"boxes must be int32 [{n}, 4] (top, left, h, w)")
+    if n and int(boxes[:, 2:].min()) < 1:
+        raise ValueError("boxes need h, w >= 1")
+
+
+def reference_crop_resize(x_u8: torch.Tensor, boxes: torch.Tensor, flip: torch.Tensor | None,
+                          size, mean, std, round_u8: bool = True,
+                          fill: float = 0.0) -> torch.Tensor:
+    """torch implementation of image_crop_resize (the CPU path): pad with ``fill`` as far as
+    the boxes reach, slice each sample's box, antialiased bilinear resize, round, flip,
+    normalise; [B,H,W,C] uint8 -> [B,C,Ho,Wo] float32."""
+    B, H, W, _ = x_u8.shape
+    bx = boxes.tolist()
+    pt = max([0] + [-t for t, _, _, _ in bx])
+    pl = max([0] + [-l for _, l, _, _ in bx])
+    pb = max([0] + [t + h - H for t, _, h, _ in bx])
+    pr = max([0] + [l + w - W for _, l, _, w in bx])
+    x = F.pad(x_u8.permute(0, 3, 1, 2).float(), (pl, pr, pt, pb), value=float(fill))
+    y = torch.cat([F.interpolate(x[b:b + 1, :, t + pt:t + pt + h, l + pl:l + pl + w],
+                                 size=tuple(size), mode="bilinear", antialias=True,
+                                 align_corners=False)
+                   for b, (t, l, h, w) in enumerate(bx)]) if B else x.new_empty(0, x.shape[1], *size)
+    if round_u8:
+        y = y.round()
+    if flip is not None:
+        y = torch.where(flip.bool().view(-1, 1, 1, 1), y.flip(-1), y)
+    m = torch.tensor(mean, dtype=torch.float32, device=y.device).view(1, -1, 1, 1)
+    s = torch.tensor(std, dtype=torch.float32, device=y.device).view(1, -1, 1, 1)
+    return (y / 255.0 - m) / s
+
+
+def crop_resize(x_u8: torch.Tensor, boxes: torch.Tensor, flip: torch.Tensor | None, size,
+                mean, std, round_u8: bool = True, channels_last: bool = True,
+                fill: float = 0.0) -> torch.Tensor:
+    """Crop sample b of ``x_u8`` [B,H,W,C] to ``boxes[b] = (top, left, h, w)`` (int32; parts
+    outside the image read ``fill``), resize the crop to ``size`` with the antialiased triangle
+    filter, round like a uint8 image, flip where ``flip[b]``, normalise. On a GPU tensor this is
+    the native kernel; host boxes are validated here and uploaded without a sync, device boxes
+    are read back once by the binding to validate them."""
+    size = _norm_size(size)
+    if x_u8.is_cuda:
+        host_boxes = not boxes.is_cuda
+        if host_boxes:
+            _check_boxes(boxes, x_u8.shape[0])
+            boxes = boxes.to(x_u8.device, non_blocking=True)
+        return native().image_crop_resize(x_u8, boxes, flip, size[0], size[1], list(mean),
+                                          list(std), round_u8, channels_last, float(fill),
+                                          check_boxes=not host_boxes)
+    _check_boxes(boxes, x_u8.shape[0])
+    y = reference_crop_resize(x_u8, boxes, flip, size, mean, std, round_u8, fill)
+    return y.contiguous(memory_format=torch.channels_last) if channels_last else y
+
+
+def resized_crop_boxes(n: int, H: int, W: int, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3),
+                       generator: torch.Generator | None = None) -> torch.Tensor:
+    """RandomResizedCrop's boxes (torchvision's rule), int32 [n, 4] = (top, left, h, w): area
+    fraction uniform in ``scale``, aspect ratio log-uniform in ``ratio``, w = round(sqrt(area r)),
+    h = round(sqrt(area / r)); of ten tries per sample (one [n, 10] draw) the first that fits the
+    image is taken, else the central crop clamped to the ratio bounds; uniform top-left."""
+    tries = 10
+    u = torch.rand(2, n, tries, generator=generator, dtype=torch.float64)
+    pos = torch.rand(n, 2, generator=generator, dtype=torch.float64)
+    area = H * W * (scale[0] + (scale[1] - scale[0]) * u[0])
+    lr0, lr1 = float(np.log(ratio[0])), float(np.log(ratio[1]))
+    r = torch.exp(lr0 + (lr1 - lr0) * u[1])
+    w = torch.round(torch.sqrt(area * r)).long()
+    h = torch.round(torch.sqrt(area / r)).long()
+    ok = (w > 0) & (w <= W) & (h > 0) & (h <= H)
+    first = ok.int().argmax(1, keepdim=True)  # index of the first valid try (0 if none)
+    any_ok = ok.any(1)
+    w, h = w.gather(1, first).squeeze(1), h.gather(1, first).squeeze(1)
+    top = torch.floor(pos[:, 0] * (H - h + 1).clamp(min=1)).long()
+    left = torch.floor(pos[:, 1] * (W - w + 1).clamp(min=1)).long()
+    # fallback: whole image, cut centrally to the nearest allowed ratio
+    if W / H < min(ratio):
+        fw, fh = W, int(round(W / min(ratio)))
+    elif W / H > max(ratio):
+        fh, fw = H, int(round(H * max(ratio)))
+    else:
+        fw, fh = W, H
+    fh, fw = min(max(fh, 1), H), min(max(fw, 1), W)
+    fb = torch.tensor([(H - fh) // 2, (W - fw) // 2, fh, fw])
+    box = torch.stack([top, left, h, w], 1)
+    return torch.where(any_ok.view(-1, 1), box, fb.view(1, 4)).to(torch.int32)
+
+
+def pad_crop_boxes(n: int, H: int, W: int, size, padding: int,
+                   generator: torch.Generator | None = None) -> torch.Tensor:
+    """RandomCrop(size, padding)'s boxes: top-left uniform in [-padding, H + padding - size]."""
+    sh, sw = _norm_size(size)
+    if sh > H + 2 * padding or sw > W + 2 * padding:
+        raise ValueError("crop size larger than the padded image")
+    top = torch.randint(-padding, H + padding - sh + 1, (n,), generator=generator)
+    left = torch.randint(-padding, W + padding - sw + 1, (n,), generator=generator)
+    return torch.stack([top, left, torch.full_like(top, sh), torch.full_like(top, sw)],
+                       1).to(torch.int32)
+
+
+def center_crop_boxes(n: int, H: int, W: int, fraction: float = 0.875) -> torch.Tensor:
+    """The central ``fraction`` of each side (224 of 256 by default), the usual evaluation crop."""
+    h, w = max(1, int(round(H * fraction))), max(1, int(round(W * fraction)))
+    return torch.tensor([[(H - h) // 2, (W - w) // 2, h, w]], dtype=torch.int32).repeat(n, 1)
+
+
+class CropTransform:
+    """RandomResizedCrop / RandomCrop(padding) / centre crop to ``size`` +
+    RandomHorizontalFlip(flip_p) + ToTensor + Normalize(mean, std); called like ImageTransform.
+
+    The boxes of each batch come from the transform's own CPU generator, which ``start_epoch``
+    reseeds (PrefetchLoader does so with its per-(seed, epoch) value), and reach the GPU through
+    a pinned buffer and a non-blocking copy: no host sync."""
+
+    def __init__(self, size=224, crop: str = "random_resized", scale=(0.08, 1.0),
+                 ratio=(3 / 4, 4 / 3), padding: int = 4, fraction: float = 0.875,
+                 flip_p: float = 0.5, mean=CIFAR_MEAN, std=CIFAR_STD, round_u8: bool = True,
+                 channels_last: bool = True):
+        if crop not in ("random_resized", "random_pad", "center"):
+            raise ValueError(f"unknown crop {crop!r}")
+        self.size, self.crop = _norm_size(size), crop
+        self.scale, self.ratio = tuple(scale), tuple(ratio)
+        self.padding, self.fraction = int(padding), float(fraction)
+        self.flip_p, self.mean, self.std = float(flip_p), tuple(mean), tuple(std)
+        self.round_u8, self.channels_last = round_u8, channels_last
+        self._gen = torch.Generator().manual_seed(0)
+
+    def start_epoch(self, seed: int) -> None:
+        self._gen.manual_seed(int(seed))
+
+    def boxes(self, n: int, H: int, W: int) -> torch.Tensor:
+        if self.crop == "random_resized":
+            return resized_crop_boxes(n, H, W, self.scale, self.ratio, self._gen)
+        if self.crop == "random_pad":
+            return pad_crop_boxes(n, H, W, self.size, self.padding, self._gen)
+        return center_crop_boxes(n, H, W, self.fraction)
+
+    def __call__(self, x_u8: torch.Tensor, flip: torch.Tensor | None) -> torch.Tensor:
+        n, H, W, _ = x_u8.shape
+        boxes = self.boxes(n, H, W)
+        if x_u8.is_cuda:
+            # torch's pinned-host cache keeps the buffer alive until the copy has run
+            boxes = torch.empty_like(boxes, pin_memory=True).copy_(boxes)
+        return crop_resize(x_u8, boxes, flip if self.flip_p > 0 else None, self.size, self.mean,
+                           self.std, self.round_u8, self.channels_last)
+
+
 def _epoch_seed(seed: int, epoch: int) -> int:
     return (int(seed) * 1000003 + int(epoch) * 7919 + 12345) & 0xFFFFFFFFFFFF
 
@@ -197,6 +352,8 @@ class PrefetchLoader:
         self._passes += 1
         self._native.start_epoch(idx, self.drop_last, _epoch_seed(self.seed, epoch),
                                  self.transform.flip_p)
+        if hasattr(self.transform, "start_epoch"):
+            self.transform.start_epoch(_epoch_seed(self.seed, epoch))
         h, w, c = self.dataset.hwc
         dev = str(self.device)
         while True:
