@@ -97,6 +97,10 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
             if s.name == "image_crop.hip":
                 # keep its fp32 math on scalar VALU: no packed-fp32 (v_pk_*_f32) instructions
                 extra = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+            if s.name == "attention.hip":
+                # both: its K loops split on the VALU beside MFMAs, and no packed-fp32 math
+                extra = ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang",
+                         "-packed-fp32-ops"]
             jobs_list.append([hipcc, f"--offload-arch={ARCH}", *common, "-ffp-contract=fast",
                               *extra, "-c", str(s), "-o", str(o)])
     for s in cpp_srcs:

@@ -1330,6 +1330,86 @@ std::vector<c10::optional<Tensor>> gn_bwd_op(
   return {opt(dx), opt(dres), dw, db};
 }
 
+// ------------------------------------------------------------------------------------ attention
+// A [B, H, S, D] float32 GPU tensor the attention kernels read or write in place through its
+// strides: unit inner stride, every row 16-byte aligned.
+static AttnT attn_view(const Tensor& t, int64_t B, int64_t H, int64_t S, int64_t D,
+                       const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.dim() == 4, what,
+              " must be a 4-D float32 GPU tensor");
+  TORCH_CHECK(t.size(0) == B && t.size(1) == H && t.size(2) == S && t.size(3) == D, what,
+              " must be [", B, ", ", H, ", ", S, ", ", D, "]");
+  TORCH_CHECK(t.stride(3) == 1 && t.stride(0) % 4 == 0 && t.stride(1) % 4 == 0 &&
+                  t.stride(2) % 4 == 0 && ((uintptr_t)t.data_ptr() & 15) == 0, what,
+              " needs unit inner stride and 16-byte aligned rows (attn_copy4d makes such a copy)");
+  return AttnT{t.data_ptr<float>(), t.stride(0), t.stride(1), t.stride(2)};
+}
+
+struct AttnDims {
+  int B, H, Sq, Sk, D;
+};
+
+static AttnDims attn_dims(const Tensor& q, const Tensor& k, const char* op) {
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, op, ": q, k, v must be [B, H, S, D]");
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), D = q.size(3), Sk = k.size(2);
+  TORCH_CHECK(D == 32 || D == 64, op, ": head sizes 32 and 64 only (got ", D, ")");
+  TORCH_CHECK(B >= 1 && H >= 1 && Sq >= 1 && Sk >= 1, op, ": empty input");
+  TORCH_CHECK(B * H <= 65535, op, ": B * H must be <= 65535 (got ", B * H, ")");
+  TORCH_CHECK(Sq < (1L << 24) && Sk < (1L << 24), op, ": sequence too long");
+  return {(int)B, (int)H, (int)Sq, (int)Sk, (int)D};
+}
+
+// a fresh [B, H, S, D] tensor whose memory is [B, S, H, D]
+static Tensor attn_empty(const Tensor& like, int64_t B, int64_t H, int64_t S, int64_t D) {
+  return at::empty({B, S, H, D}, like.options()).permute({0, 2, 1, 3});
+}
+
+// -> [o, lse]: o is [B, H, Sq, D] over [B, Sq, H, D] memory, lse [B, H, Sq]
+std::vector<Tensor> attn_fwd_op(const Tensor& q, const Tensor& k, const Tensor& v, double scale) {
+  const AttnDims d = attn_dims(q, k, "attn_fwd");
+  const AttnT qv = attn_view(q, d.B, d.H, d.Sq, d.D, "attn_fwd: q");
+  const AttnT kv = attn_view(k, d.B, d.H, d.Sk, d.D, "attn_fwd: k");
+  const AttnT vv = attn_view(v, d.B, d.H, d.Sk, d.D, "attn_fwd: v");
+  auto o = attn_empty(q, d.B, d.H, d.Sq, d.D);
+  auto lse = at::empty({d.B, d.H, d.Sq}, q.options());
+  attn_fwd(qv, kv, vv, attn_view(o, d.B, d.H, d.Sq, d.D, "attn_fwd: o"), lse.data_ptr<float>(),
+           d.B, d.H, d.Sq, d.Sk, d.D, (float)scale, cur_stream());
+  return {o, lse};
+}
+
+// dq / dk / dv are written in place through their strides (views of one packed gradient, or
+// fresh tensors): every element exactly once
+void attn_bwd_op(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+                 const Tensor& o, const Tensor& lse, double scale, Tensor dq, Tensor dk,
+                 Tensor dv) {
+  const AttnDims d = attn_dims(q, k, "attn_bwd");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.numel() == (int64_t)d.B * d.H * d.Sq, "attn_bwd: lse must be [B, H, Sq]");
+  auto delta = at::empty({2, lse.numel()}, lse.options());
+  attn_bwd(attn_view(dout, d.B, d.H, d.Sq, d.D, "attn_bwd: dout"),
+           attn_view(q, d.B, d.H, d.Sq, d.D, "attn_bwd: q"),
+           attn_view(k, d.B, d.H, d.Sk, d.D, "attn_bwd: k"),
+           attn_view(v, d.B, d.H, d.Sk, d.D, "attn_bwd: v"),
+           attn_view(o, d.B, d.H, d.Sq, d.D, "attn_bwd: o"), lse.data_ptr<float>(),
+           delta.data_ptr<float>(), attn_view(dq, d.B, d.H, d.Sq, d.D, "attn_bwd: dq"),
+           attn_view(dk, d.B, d.H, d.Sk, d.D, "attn_bwd: dk"),
+           attn_view(dv, d.B, d.H, d.Sk, d.D, "attn_bwd: dv"), d.B, d.H, d.Sq, d.Sk, d.D,
+           (float)scale, cur_stream());
+}
+
+// any-stride [B, H, S, D] -> a copy the kernels can read: [B, H, S, D] over [B, S, H, D] memory
+Tensor attn_copy4d_op(const Tensor& t) {
+  CHECK_GPU(t); CHECK_F32(t);
+  TORCH_CHECK(t.dim() == 4 && t.numel() > 0, "attn_copy4d: a non-empty [B, H, S, D] tensor");
+  TORCH_CHECK(t.size(1) < (1L << 31) && t.size(2) < (1L << 31) && t.size(3) < (1L << 31),
+              "attn_copy4d: dimension too large");
+  auto out = attn_empty(t, t.size(0), t.size(1), t.size(2), t.size(3));
+  attn_copy4d(t.data_ptr<float>(), t.stride(0), t.stride(1), t.stride(2), t.stride(3),
+              out.data_ptr<float>(), (int)t.size(0), (int)t.size(1), (int)t.size(2),
+              (int)t.size(3), cur_stream());
+  return out;
+}
+
 // ---------------------------------------------------------------------------------- conv / pool
 ConvGeom conv_geom(const std::vector<int64_t>& xs, const std::vector<int64_t>& ws,
                    int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
@@ -2675,6 +2755,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("y_relu") = py::none(), py::arg("mask") = py::none(),
         py::arg("nhwc") = false, py::arg("want_dx") = true, py::arg("want_dres") = false,
         py::arg("dw") = py::none(), py::arg("db") = py::none());
+
+  m.def("attn_fwd", &attn_fwd_op, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"));
+  m.def("attn_bwd", &attn_bwd_op, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"),
+        py::arg("dv"));
+  m.def("attn_copy4d", &attn_copy4d_op, py::arg("t"));
 
   m.def("rccl_unique_id", &unique_id_op);
   m.def("debug_spin_ms", [](int ms) { debug_spin_ms(ms, cur_stream()); });

@@ -499,4 +499,28 @@ void gn_bwd(const float* dy, const float* x, const float* stats, const float* w,
             float* ws, float* ab, float* gs, float* dx, float* dres, float* dw, float* db,
             hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------
+// Fused attention (csrc/attention.hip): o = softmax(scale * q k^T) v per (batch, head), D = 32 or
+// 64, every GEMM an fp32 GEMM on the bf16 matrix core (split_bf16.h), the score matrix never
+// written. A tensor is [B][H][S][D] through strides (elements): unit inner stride, rows 16-byte
+// aligned. No atomics; the partition depends on (Sq, Sk, D) only and a (b, h) never shares a
+// workgroup, so results repeat bitwise and a sample does not see its batch.
+// ------------------------------------------------------------------------------------------------
+struct AttnT {
+  const float* p;
+  long sb, sh, ss;  // batch, head, row strides
+};
+// lse [B*H][Sq] out: log-sum-exp of the scaled scores of each query, saved for the backward
+void attn_fwd(const AttnT& q, const AttnT& k, const AttnT& v, const AttnT& o, float* lse, int B,
+              int H, int Sq, int Sk, int D, float scale, hipStream_t s);
+// three launches: delta [2][B*H][Sq] = rowsum(dO * o) in the operand order of each backward
+// kernel's dP (scratch out), then dq (a workgroup owns a query tile) and dk / dv (a workgroup
+// owns a key tile); each output element is written once
+void attn_bwd(const AttnT& dout, const AttnT& q, const AttnT& k, const AttnT& v, const AttnT& o,
+              const float* lse, float* delta, const AttnT& dq, const AttnT& dk, const AttnT& dv,
+              int B, int H, int Sq, int Sk, int D, float scale, hipStream_t s);
+// src [B][H][S][D] with any strides (elements) -> dst dense [B][S][H][D]
+void attn_copy4d(const float* src, long sb, long sh, long ss, long sd, float* dst, int B, int H,
+                 int S, int D, hipStream_t s);
+
 }  // namespace tdp

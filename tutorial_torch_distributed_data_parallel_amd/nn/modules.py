@@ -251,6 +251,60 @@ class GELU(nn.GELU):
         return ops.gelu(x, approximate=self.approximate)
 
 
+class MultiheadAttention(nn.Module):
+    """Self-attention with ``torch.nn.MultiheadAttention``'s parameters (``in_proj_weight``
+    [3E, E], ``in_proj_bias``, ``out_proj.weight``, ``out_proj.bias``, torch's initialisation), so
+    state dicts load in both directions. One ``ops.linear`` for the packed projection, the fused
+    attention kernels on it in place (``ops.attention_qkvpacked``), then ``out_proj``. Under
+    ``tdp.autocast`` the two projections run in bf16 and the attention core stays float32 (a bf16
+    core is a follow-up). Masks, dropout, attention weights, cross-attention and
+    ``batch_first=False`` raise ``NotImplementedError``."""
+
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True,
+                 batch_first: bool = True, device=None, *, dropout: float = 0.0, kdim=None,
+                 vdim=None):
+        super().__init__()
+        if dropout > 0:
+            raise NotImplementedError("MultiheadAttention: dropout > 0 has no kernel")
+        if not batch_first:
+            raise NotImplementedError("MultiheadAttention: batch_first=False is not supported")
+        if (kdim is not None and kdim != embed_dim) or (vdim is not None and vdim != embed_dim):
+            raise NotImplementedError("MultiheadAttention: kdim / vdim (cross-attention) are not "
+                                      "supported")
+        if embed_dim % num_heads:
+            raise ValueError("MultiheadAttention: embed_dim must be divisible by num_heads")
+        if embed_dim // num_heads not in ops.attention.HEAD_SIZES:
+            raise NotImplementedError(
+                f"MultiheadAttention: head size {embed_dim // num_heads} has no kernel; the "
+                f"supported head sizes are 32 and 64")
+        self.embed_dim, self.num_heads, self.batch_first = embed_dim, num_heads, True
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim, device=device))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim, device=device)) \
+            if bias else None
+        self.out_proj = Linear(embed_dim, embed_dim, bias=bias, device=device)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        if bias:
+            nn.init.zeros_(self.out_proj.bias)
+
+    def forward(self, x, key=None, value=None, key_padding_mask=None, need_weights=False,
+                attn_mask=None, is_causal=False):
+        if (key is not None and key is not x) or (value is not None and value is not x):
+            raise NotImplementedError("MultiheadAttention: self-attention only")
+        if need_weights:
+            raise NotImplementedError("MultiheadAttention: need_weights=True would write the "
+                                      "score matrix the kernels never form")
+        if key_padding_mask is not None or attn_mask is not None or is_causal:
+            raise NotImplementedError("MultiheadAttention: masks and is_causal have no kernel")
+        if x.dim() != 3 or x.shape[2] != self.embed_dim:
+            raise ValueError(f"MultiheadAttention: expected [B, S, {self.embed_dim}] "
+                             f"(got {tuple(x.shape)})")
+        qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
+        return self.out_proj(ops.attention_qkvpacked(qkv, self.num_heads)), None
+
+    def extra_repr(self) -> str:
+        return f"embed_dim={self.embed_dim}, num_heads={self.num_heads}"
+
+
 class StochasticDepth(nn.Module):
     """torchvision's ``StochasticDepth(p, mode)`` (``ops.stochastic_depth``); ``"row"`` only."""
 
