@@ -94,7 +94,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
             # the split-bf16 GEMM keeps its f32 residual subtractions scalar: packed f32 VALU
             # (v_pk_add_f32) costs ~4x a v_sub_f32's issue slot beside MFMAs
             extra = ["-fno-slp-vectorize"] if s.name in ("gemm_f32_fast.hip", "gemm_planes.hip", "gemm_emu8.hip") else []
-            if s.name == "image_crop.hip":
+            if s.name in ("image_crop.hip", "weight_std.hip"):
                 # keep its fp32 math on scalar VALU: no packed-fp32 (v_pk_*_f32) instructions
                 extra = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
             if s.name == "attention.hip":

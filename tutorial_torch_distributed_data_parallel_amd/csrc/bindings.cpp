@@ -1330,6 +1330,44 @@ std::vector<c10::optional<Tensor>> gn_bwd_op(
   return {opt(dx), opt(dres), dw, db};
 }
 
+// ------------------------------------------------------------------------ weight standardisation
+// A float32 GPU convolution weight [Cout, Cg, R, S] in one of its two memory layouts (contiguous
+// or channels_last): filter o is then the dense run of K = Cg*R*S floats at o*K.
+static void ws_weight(const Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.dim() == 4, what,
+              " must be a 4-D float32 GPU tensor");
+  TORCH_CHECK(t.is_contiguous() || t.is_contiguous(at::MemoryFormat::ChannelsLast), what,
+              " must be contiguous or channels_last (each filter one dense run)");
+  TORCH_CHECK(t.numel() > 0 && t.size(0) < (1L << 31) && t.numel() / t.size(0) < (1L << 31),
+              what, " must have 1 .. 2^31 - 1 filters of 1 .. 2^31 - 1 elements");
+}
+
+// -> [w_hat (the weight's strides), rstd [Cout]]
+std::vector<Tensor> ws_fwd_op(const Tensor& w, double eps) {
+  ws_weight(w, "ws_fwd: weight");
+  auto out = at::empty_like(w);
+  TORCH_CHECK(out.strides() == w.strides(), "ws_fwd: could not keep the weight's strides");
+  const int rows = (int)w.size(0), K = (int)(w.numel() / w.size(0));
+  auto rstd = at::empty({(int64_t)rows}, w.options());
+  ws_fwd(w.data_ptr<float>(), rows, K, (float)eps, out.data_ptr<float>(),
+         rstd.data_ptr<float>(), cur_stream());
+  return {out, rstd};
+}
+
+// dw (given: the parameter's gradient slot) is written in place
+void ws_bwd_op(const Tensor& g, const Tensor& what, const Tensor& rstd, const Tensor& dw) {
+  ws_weight(what, "ws_bwd: w_hat");
+  ws_weight(g, "ws_bwd: g");
+  ws_weight(dw, "ws_bwd: dw");
+  TORCH_CHECK(g.sizes() == what.sizes() && g.strides() == what.strides() &&
+                  dw.sizes() == what.sizes() && dw.strides() == what.strides(),
+              "ws_bwd: g and dw must have w_hat's shape and strides");
+  const int rows = (int)what.size(0), K = (int)(what.numel() / what.size(0));
+  opt_vec(c10::optional<Tensor>(rstd), rows, "ws_bwd: rstd");
+  ws_bwd(g.data_ptr<float>(), what.data_ptr<float>(), rstd.data_ptr<float>(), rows, K,
+         dw.data_ptr<float>(), cur_stream());
+}
+
 // ------------------------------------------------------------------------------------ attention
 // A [B, H, S, D] float32 GPU tensor the attention kernels read or write in place through its
 // strides: unit inner stride, every row 16-byte aligned.
@@ -2755,6 +2793,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("y_relu") = py::none(), py::arg("mask") = py::none(),
         py::arg("nhwc") = false, py::arg("want_dx") = true, py::arg("want_dres") = false,
         py::arg("dw") = py::none(), py::arg("db") = py::none());
+
+  m.def("ws_fwd", &ws_fwd_op, py::arg("w"), py::arg("eps"));
+  m.def("ws_bwd", &ws_bwd_op, py::arg("g"), py::arg("w_hat"), py::arg("rstd"), py::arg("dw"));
+  m.attr("ws_cap") = kWsCap;
 
   m.def("attn_fwd", &attn_fwd_op, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"));
   m.def("attn_bwd", &attn_bwd_op, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),

@@ -523,4 +523,18 @@ void attn_bwd(const AttnT& dout, const AttnT& q, const AttnT& k, const AttnT& v,
 void attn_copy4d(const float* src, long sb, long sh, long ss, long sd, float* dst, int B, int H,
                  int S, int D, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------
+// Weight standardisation (csrc/weight_std.hip) of a dense [rows][K] matrix (a convolution weight:
+// filter o is the K = Cg*R*S floats at o*K in either of its memory layouts). One wave per row;
+// rows of K <= kWsCap floats stay in registers when K % 4 == 0 and every pointer is 16-byte
+// aligned, longer ones are re-read per pass, anything else takes 4-byte accesses. No atomics, no
+// scratch; a row's reduction order depends on K alone.
+// ------------------------------------------------------------------------------------------------
+constexpr int kWsCap = 4608;  // longest register-resident row (ResNet-50's 512x3x3 filter)
+// out[o] = (w[o] - mean_o) * rstd_o, rstd[o] = 1 / sqrt(var_o + eps) (biased variance)
+void ws_fwd(const float* w, int rows, int K, float eps, float* out, float* rstd, hipStream_t s);
+// dw[o] = rstd_o * (g[o] - mean(g[o]) - what[o] * mean(g[o] * what[o])), what = ws_fwd's out
+void ws_bwd(const float* g, const float* what, const float* rstd, int rows, int K, float* dw,
+            hipStream_t s);
+
 }  // namespace tdp

@@ -28,6 +28,10 @@ def build_model(name: str, num_classes: int = 10, device=None) -> torch.nn.Modul
         from .resnet import resnet50_gn
 
         return resnet50_gn(num_classes=num_classes, device=device)
+    if name in ("resnet50_gn_ws", "resnet-50-gn-ws"):
+        from .resnet import resnet50_gn_ws
+
+        return resnet50_gn_ws(num_classes=num_classes, device=device)
     if name == "resnext50_32x4d":
         from .resnet import resnext50_32x4d
 

@@ -14,6 +14,12 @@ Weights use torchvision's initialisation (Kaiming-normal fan_out convs, BN gamma
 ``resnet50_gn`` uses ``GroupNorm(32, channels)`` (csrc/groupnorm.hip) -- the network
 ``torchvision.models.resnet50(norm_layer=lambda c: nn.GroupNorm(32, c))`` builds, with the same
 attribute names (``bn1`` ...), no buffers, and no batch statistics asked of the convolutions.
+
+``conv_layer`` swaps the convolution class the same way (default ``Conv2d``). ``resnet50_gn_ws``
+builds every convolution, the stem and the downsample paths included, as ``StdConv2d``
+(weight standardisation, csrc/weight_std.hip) over GroupNorm: same keys, shapes and
+initialisation as ``resnet50_gn``. A ``StdConv2d`` is a ``Conv2d``, so the fused residual join
+and the shared input-gradient sink are taken as before.
 """
 from __future__ import annotations
 
@@ -22,7 +28,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops._grad import SharedGrad, fork
-from ..nn import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, GroupNorm, Linear, MaxPool2d
+from ..nn import (AdaptiveAvgPool2d, BatchNorm2d, Conv2d, GroupNorm, Linear, MaxPool2d,
+                  StdConv2d)
 
 
 def _batch_norm(channels, relu=False, device=None):
@@ -33,17 +40,18 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, device=None, groups=1,
-                 base_width=64, norm_layer=None):
+                 base_width=64, norm_layer=None, conv_layer=None):
         super().__init__()
         norm_layer = norm_layer or _batch_norm
+        conv = conv_layer or Conv2d
         kw = dict(bias=False, device=device)
         # torchvision's width rule: ResNeXt widens the 3x3 and splits it into groups
         width = int(planes * base_width / 64) * groups
-        self.conv1 = Conv2d(inplanes, width, 1, **kw)
+        self.conv1 = conv(inplanes, width, 1, **kw)
         self.bn1 = norm_layer(width, relu=True, device=device)
-        self.conv2 = Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, **kw)
+        self.conv2 = conv(width, width, 3, stride=stride, padding=1, groups=groups, **kw)
         self.bn2 = norm_layer(width, relu=True, device=device)
-        self.conv3 = Conv2d(width, planes * 4, 1, **kw)
+        self.conv3 = conv(width, planes * 4, 1, **kw)
         self.bn3 = norm_layer(planes * 4, device=device)
         self.downsample = downsample
         self.stride = stride
@@ -88,12 +96,13 @@ def _takes_sink(m) -> bool:
 
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes: int = 10, device=None, groups=1,
-                 width_per_group=64, norm_layer=None):
+                 width_per_group=64, norm_layer=None, conv_layer=None):
         super().__init__()
         self._norm_layer = norm_layer or _batch_norm
+        self._conv_layer = conv_layer or Conv2d
         self.inplanes = 64
         self.groups, self.base_width = groups, width_per_group
-        self.conv1 = Conv2d(3, 64, 7, stride=2, padding=3, bias=False, device=device)
+        self.conv1 = self._conv_layer(3, 64, 7, stride=2, padding=3, bias=False, device=device)
         self.bn1 = self._norm_layer(64, relu=True, device=device)
         self.maxpool = MaxPool2d(kernel_size=3, stride=2, padding=1)
         self.layer1 = self._make_layer(64, layers[0], 1, device)
@@ -113,7 +122,7 @@ class ResNet(nn.Module):
             elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
-        del self._norm_layer  # construction only (a closure would not pickle with the model)
+        del self._norm_layer, self._conv_layer  # construction only (a closure would not pickle)
 
     def _conv_norm_pairs(self):
         yield self.conv1, self.bn1
@@ -129,10 +138,11 @@ class ResNet(nn.Module):
         downsample = None
         if stride != 1 or self.inplanes != planes * Bottleneck.expansion:
             downsample = nn.Sequential(
-                Conv2d(self.inplanes, planes * 4, 1, stride=stride, bias=False, device=device),
+                self._conv_layer(self.inplanes, planes * 4, 1, stride=stride, bias=False,
+                                 device=device),
                 self._norm_layer(planes * 4, device=device))
         kw = dict(device=device, groups=self.groups, base_width=self.base_width,
-                  norm_layer=self._norm_layer)
+                  norm_layer=self._norm_layer, conv_layer=self._conv_layer)
         layers = [Bottleneck(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * 4
         for _ in range(1, blocks):
@@ -165,3 +175,14 @@ def resnet50_gn(num_classes: int = 10, device=None, groups: int = 32) -> ResNet:
         return GroupNorm(groups, channels, relu=relu, device=device)
 
     return ResNet((3, 4, 6, 3), num_classes=num_classes, device=device, norm_layer=norm)
+
+
+def resnet50_gn_ws(num_classes: int = 10, device=None, groups: int = 32) -> ResNet:
+    """``resnet50_gn`` with every convolution a ``StdConv2d`` (weight standardisation): the
+    GroupNorm + WS pairing of Qiao et al. and of Big Transfer's ResNet-50x1. Keys, shapes,
+    parameter count and initialisation are ``resnet50_gn``'s."""
+    def norm(channels, relu=False, device=None):
+        return GroupNorm(groups, channels, relu=relu, device=device)
+
+    return ResNet((3, 4, 6, 3), num_classes=num_classes, device=device, norm_layer=norm,
+                  conv_layer=StdConv2d)

@@ -62,6 +62,36 @@ class Conv2d(nn.Conv2d):
         return super().extra_repr() + (", relu=True" if self.relu else "")
 
 
+class StdConv2d(Conv2d):
+    """``Conv2d`` on the standardised weight (``ops.weight_standardize``: every output filter at
+    zero mean and unit variance, no gain): GroupNorm's companion in the recipes that train at
+    small per-rank batches. Constructor and ``state_dict`` keys are ``Conv2d``'s (plus ``eps``),
+    so a checkpoint moves between the two.
+
+    The parameter stays the raw weight. ``w_hat`` is an ordinary tensor: the convolution writes
+    its gradient like any activation gradient, and the op's backward turns that into the
+    parameter's gradient, in its DDP gradient-arena slot. Inside ``tdp.autocast`` the
+    standardisation stays float32 on the master weight; the convolution then rounds ``w_hat`` to
+    bf16 as it rounds any weight.
+
+    ``w_hat`` is recomputed on every forward, in eval mode too. It must not be cached keyed on
+    ``weight._version``: the native optimizer kernels update parameters in place without touching
+    that counter, so such a cache would serve stale weights."""
+
+    def __init__(self, *args, eps: float = 1e-5, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.eps = eps
+
+    def forward(self, x, grad_into=None):
+        w_hat = ops.weight_standardize(self.weight, self.eps)
+        return ops.conv2d(x, w_hat, self.bias, self.stride, self.padding, relu=self.relu,
+                          grad_into=grad_into, bn_stats=self.bn_stats and self.training,
+                          groups=self.groups)
+
+    def extra_repr(self) -> str:
+        return super().extra_repr() + f", eps={self.eps}"
+
+
 class ReLU(nn.ReLU):
     """Standalone ReLU (models fuse it into the producer where possible)."""
 
