@@ -570,6 +570,96 @@ void count_correct_op(const Tensor& logits, const Tensor& labels, Tensor& acc) {
                 (int)logits.size(1), logits.stride(0), acc.data_ptr<float>(), cur_stream());
 }
 
+// class-probability targets (csrc/loss_soft.hip). target: dense float32 [B, C], or none for the
+// pair form (ya, yb int64 [B], lam float32 [B]). Returns {loss, rows [2, B] (per-row loss |
+// correct flag), dpre [B, C] when with_grad}.
+std::vector<Tensor> soft_ce_fwd_op(const Tensor& logits, const c10::optional<Tensor>& target,
+                                   const c10::optional<Tensor>& ya,
+                                   const c10::optional<Tensor>& yb,
+                                   const c10::optional<Tensor>& lam, double smoothing, bool mean,
+                                   const c10::optional<Tensor>& acc, bool with_grad) {
+  CHECK_GPU(logits); CHECK_F32(logits); CHECK_ROWMAJOR(logits);
+  const int64_t B = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(B >= 1 && C >= 1 && B < (1LL << 31) - 4 && C < (1LL << 31) - 4,
+              "soft_ce_fwd: logits must be a non-empty [B, C] matrix");
+  TORCH_CHECK(smoothing >= 0.0 && smoothing <= 1.0, "soft_ce_fwd: label_smoothing in [0, 1]");
+  const bool dense = target.has_value() && target->defined();
+  long ldt = 0;
+  const float* tp = nullptr;
+  const int64_t *yap = nullptr, *ybp = nullptr;
+  const float* lamp = nullptr;
+  if (dense) {
+    tp = opt_mat(target, B, C, &ldt, "soft_ce_fwd: target");
+    TORCH_CHECK(target->device() == logits.device(), "soft_ce_fwd: target on another device");
+  } else {
+    TORCH_CHECK(ya.has_value() && yb.has_value() && lam.has_value(),
+                "soft_ce_fwd: a dense target or (ya, yb, lam)");
+    for (const Tensor* y : {&*ya, &*yb}) {
+      TORCH_CHECK(y->is_cuda() && y->device() == logits.device() &&
+                      y->scalar_type() == at::kLong && y->is_contiguous() && y->numel() == B,
+                  "soft_ce_fwd: ya, yb must be contiguous int64 [B] on the logits' device");
+    }
+    TORCH_CHECK(lam->device() == logits.device(), "soft_ce_fwd: lam on another device");
+    lamp = opt_vec(lam, B, "soft_ce_fwd: lam");
+    yap = ya->data_ptr<int64_t>();
+    ybp = yb->data_ptr<int64_t>();
+  }
+  float* accp = nullptr;
+  if (acc.has_value() && acc->defined()) {
+    CHECK_GPU(*acc); CHECK_F32(*acc);
+    TORCH_CHECK(acc->numel() >= 3, "acc needs 3 floats");
+    accp = acc->data_ptr<float>();
+  }
+  auto loss = at::empty({}, logits.options());
+  auto rows = at::empty({2, B}, logits.options());
+  Tensor d;
+  if (with_grad) d = at::empty({B, C}, logits.options());
+  soft_ce_fwd(logits.data_ptr<float>(), logits.stride(0), tp, ldt, yap, ybp, lamp, (int)B, (int)C,
+              (float)smoothing, mean, rows.data_ptr<float>(), loss.data_ptr<float>(), accp,
+              with_grad ? d.data_ptr<float>() : nullptr, cur_stream());
+  if (with_grad) return {loss, rows, d};
+  return {loss, rows};
+}
+
+Tensor soft_ce_scale_op(const Tensor& dpre, const Tensor& gout) {
+  CHECK_GPU(dpre); CHECK_F32(dpre); CHECK_CONTIG(dpre);
+  CHECK_GPU(gout); CHECK_F32(gout);
+  TORCH_CHECK(gout.numel() == 1 && gout.device() == dpre.device(),
+              "soft_ce_scale: gout must be one float on dpre's device");
+  auto d = at::empty_like(dpre);
+  soft_ce_scale(dpre.data_ptr<float>(), gout.data_ptr<float>(), dpre.numel(),
+                d.data_ptr<float>(), cur_stream());
+  return d;
+}
+
+// ---------------------------------------------------------------------------- MixUp / CutMix
+Tensor mix_batch_op(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& boxes) {
+  CHECK_GPU(x); CHECK_F32(x);
+  TORCH_CHECK(x.dim() == 4 && x.numel() > 0, "mix_batch: x must be a non-empty [N, C, H, W]");
+  const bool nchw = x.is_contiguous();
+  const bool nhwc = !nchw && x.is_contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(nchw || nhwc, "mix_batch: x must be contiguous or channels_last");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(N <= 65535, "mix_batch: at most 65535 samples per call");
+  TORCH_CHECK(C * H * W < (1LL << 31) - 4096, "mix_batch: a sample must stay below 2^31 floats");
+  for (const Tensor* t : {&perm, &lam, &boxes}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == x.device() && t->is_contiguous(),
+                "mix_batch: perm, lam and boxes must be contiguous tensors on x's device");
+  }
+  TORCH_CHECK((perm.scalar_type() == at::kLong || perm.scalar_type() == at::kInt) &&
+                  perm.dim() == 1 && perm.numel() == N, "mix_batch: perm must be int32 / int64 [N]");
+  TORCH_CHECK(lam.scalar_type() == at::kFloat && lam.dim() == 1 && lam.numel() == N,
+              "mix_batch: lam must be float32 [N]");
+  TORCH_CHECK(boxes.scalar_type() == at::kInt && boxes.dim() == 2 && boxes.size(0) == N &&
+                  boxes.size(1) == 4, "mix_batch: boxes must be int32 [N, 4] (top, left, h, w)");
+  auto out = at::empty_like(x, x.options(), at::MemoryFormat::Preserve);
+  TORCH_CHECK(out.strides() == x.strides(), "mix_batch: could not keep x's strides");
+  mix_batch(x.data_ptr<float>(), perm.data_ptr(), perm.scalar_type() == at::kLong,
+            lam.data_ptr<float>(), boxes.data_ptr<int>(), out.data_ptr<float>(), (int)N, (int)C,
+            (int)H, (int)W, nhwc, cur_stream());
+  return out;
+}
+
 // ---------------------------------------------------------------------------------- optimizers
 const float* hyper_ptr(const c10::optional<Tensor>& blk) {
   if (!blk.has_value() || !blk->defined()) return nullptr;
@@ -2797,6 +2887,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ws_fwd", &ws_fwd_op, py::arg("w"), py::arg("eps"));
   m.def("ws_bwd", &ws_bwd_op, py::arg("g"), py::arg("w_hat"), py::arg("rstd"), py::arg("dw"));
   m.attr("ws_cap") = kWsCap;
+
+  m.def("soft_ce_fwd", &soft_ce_fwd_op, py::arg("logits"), py::arg("target") = py::none(),
+        py::arg("ya") = py::none(), py::arg("yb") = py::none(), py::arg("lam") = py::none(),
+        py::arg("smoothing") = 0.0, py::arg("mean") = true, py::arg("acc") = py::none(),
+        py::arg("with_grad") = false);
+  m.def("soft_ce_scale", &soft_ce_scale_op, py::arg("dpre"), py::arg("gout"));
+  m.attr("soft_ce_cap") = kSoftCeCap;
+  m.def("mix_batch", &mix_batch_op, py::arg("x"), py::arg("perm"), py::arg("lam"),
+        py::arg("boxes"));
 
   m.def("attn_fwd", &attn_fwd_op, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"));
   m.def("attn_bwd", &attn_bwd_op, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),

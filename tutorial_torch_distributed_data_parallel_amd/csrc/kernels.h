@@ -537,4 +537,31 @@ void ws_fwd(const float* w, int rows, int K, float eps, float* out, float* rstd,
 void ws_bwd(const float* g, const float* what, const float* rstd, int rows, int K, float* dw,
             hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------
+// Cross-entropy against a class-probability target (csrc/loss_soft.hip). target != null: the
+// dense form (float [B][C], row stride ldt); target == null: the pair form, row r's target is
+// lam[r] * onehot(ya[r]) + (1 - lam[r]) * onehot(yb[r]). One wave per row; rows of C <=
+// kSoftCeCap classes stay in registers, longer ones are re-read per sweep. rows is [2][B]
+// scratch that comes back holding the per-row loss and correct flags; out_loss the mean (over B)
+// or the sum; acc (optional) += [loss sum, rows whose argmax matches the target's, B]; dpre
+// (optional, dense [B][C]) the logits gradient for an upstream gradient of exactly 1.
+// ------------------------------------------------------------------------------------------------
+constexpr int kSoftCeCap = 4096;  // longest register-resident row: 16 float4 per lane
+void soft_ce_fwd(const float* logits, long ld, const float* target, long ldt, const int64_t* ya,
+                 const int64_t* yb, const float* lam, int B, int C, float label_smoothing,
+                 bool mean, float* rows, float* out_loss, float* acc, float* dpre, hipStream_t s);
+// d[i] = gout[0] * dpre[i]
+void soft_ce_scale(const float* dpre, const float* gout, long n, float* d, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
+// MixUp / CutMix batch mixing (csrc/mix.hip) of a dense float batch, N samples of C*H*W floats in
+// the contiguous (nhwc == false) or channels_last (true) layout, out of place:
+//   out[b, :, i, j] = inside(box[b], i, j) ? x[perm[b]]
+//                     : (lam[b] == 1 ? x[b] : lam[b] x[b] + (1 - lam[b]) x[perm[b]])
+// box [N][4] = (top, left, h, w), clipped by the kernel; perm int32 or int64 (perm64), an entry
+// outside [0, N) is read as the sample itself. N <= 65535, C*H*W < 2^31 - 4096.
+// ------------------------------------------------------------------------------------------------
+void mix_batch(const float* x, const void* perm, bool perm64, const float* lam, const int* box,
+               float* out, int N, int C, int H, int W, bool nhwc, hipStream_t s);
+
 }  // namespace tdp

@@ -3,6 +3,7 @@ pipeline (native prefetcher + on-device resize / flip / normalise)."""
 from .host import (CIFAR_MEAN, CIFAR_STD, CropTransform, HostImageDataset, ImageTransform,
                    PrefetchLoader, center_crop_boxes, cifar_like_uint8, crop_resize,
                    load_cifar10_bin, pad_crop_boxes, resized_crop_boxes, write_cifar10_bin)
+from .mix import BatchMix, mix_batch
 from .sampler import BatchShardSampler, DistributedSampler
 from .synthetic import DeviceLoader, SyntheticDataset, cifar_like
 
@@ -10,4 +11,4 @@ __all__ = ["DistributedSampler", "BatchShardSampler", "SyntheticDataset", "Devic
            "cifar_like", "HostImageDataset", "ImageTransform", "PrefetchLoader",
            "cifar_like_uint8", "load_cifar10_bin", "write_cifar10_bin", "CIFAR_MEAN",
            "CIFAR_STD", "CropTransform", "crop_resize", "resized_crop_boxes", "pad_crop_boxes",
-           "center_crop_boxes"]
+           "center_crop_boxes", "BatchMix", "mix_batch"]

@@ -43,9 +43,81 @@ class _CrossEntropyFn(torch.autograd.Function):
         return d, None, None, None, None, None
 
 
+class _SoftCrossEntropyFn(torch.autograd.Function):
+    """Cross-entropy against class probabilities (csrc/loss_soft.hip): ``target`` is the dense
+    ``[B, C]`` tensor, or None for the pair form ``lam * onehot(ya) + (1 - lam) * onehot(yb)``.
+    The forward launch also writes the logits gradient for a unit upstream gradient (its scale,
+    1/B or 1, is known on the host), so a backward seeded with the cached unit seed launches
+    nothing; any other seed takes one native scale kernel. Targets get no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ya, yb, lam, smoothing: float, mean: bool, acc):
+        fused = bool(ctx.needs_input_grad[0])
+        out = native().soft_ce_fwd(logits, target, ya, yb, lam, smoothing, mean, acc,
+                                   with_grad=fused)
+        ctx.dpre = out[2] if fused else None
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        dpre, ctx.dpre = ctx.dpre, None
+        if dpre is None:
+            raise RuntimeError("soft-target cross_entropy: backward called twice")
+        if not _is_unit_seed(gout):
+            dpre = native().soft_ce_scale(dpre, gout.reshape(1).float())
+        return dpre, None, None, None, None, None, None, None
+
+
+def _soft_checks(logits: torch.Tensor, reduction: str) -> torch.Tensor:
+    if reduction not in ("mean", "sum"):
+        raise NotImplementedError("native cross_entropy supports reduction='mean'|'sum'")
+    if logits.dim() != 2:
+        raise ValueError("native cross_entropy expects [batch, classes] logits")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"native cross_entropy: float32 logits only (got {logits.dtype})")
+    return logits if logits.stride(1) == 1 else logits.contiguous()
+
+
+def _soft_acc(logits, dense, reduction, acc, label_smoothing):
+    """The CPU path's ``acc`` update for a dense probability target."""
+    with torch.no_grad():
+        acc[0] += F.cross_entropy(logits.detach(), dense, label_smoothing=label_smoothing,
+                                  reduction="sum")
+        acc[1] += (logits.argmax(1) == dense.argmax(1)).sum()
+        acc[2] += logits.shape[0]
+
+
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100,
                   label_smoothing: float = 0.0, reduction: str = "mean",
                   acc: torch.Tensor | None = None) -> torch.Tensor:
+    """``F.cross_entropy`` on the native kernels. An int64 ``[B]`` target is a class index per
+    row; a floating-point target of ``logits``' shape holds class probabilities (``ignore_index``
+    then has no meaning, as in torch). Any other target dtype raises ``TypeError``, a target of
+    any other shape ``ValueError``."""
+    if target.is_floating_point():
+        if target.shape != logits.shape:
+            raise ValueError(f"cross_entropy: a probability target must have the logits' shape "
+                             f"{tuple(logits.shape)} (got {tuple(target.shape)})")
+        if not logits.is_cuda:
+            loss = F.cross_entropy(logits, target, label_smoothing=label_smoothing,
+                                   reduction=reduction)
+            if acc is not None:
+                _soft_acc(logits, target, reduction, acc, label_smoothing)
+            return loss
+        logits = _soft_checks(logits, reduction)
+        if target.dtype != torch.float32:
+            raise TypeError(f"native cross_entropy: float32 probability targets only "
+                            f"(got {target.dtype})")
+        if target.stride(1) != 1:
+            target = target.contiguous()
+        return _SoftCrossEntropyFn.apply(logits, target.detach(), None, None, None,
+                                         float(label_smoothing), reduction == "mean", acc)
+    if target.dtype != torch.int64:
+        raise TypeError(f"cross_entropy: the target must be int64 class indices or floating-point "
+                        f"class probabilities (got {target.dtype})")
+    if target.dim() != logits.dim() - 1 or target.shape[0] != logits.shape[0]:
+        raise ValueError(f"cross_entropy: an index target must be [batch] "
+                         f"(got {tuple(target.shape)} for logits {tuple(logits.shape)})")
     if not logits.is_cuda:
         loss = F.cross_entropy(logits, target, ignore_index=ignore_index,
                                label_smoothing=label_smoothing, reduction=reduction)
@@ -66,6 +138,50 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int 
         logits = logits.contiguous()
     return _CrossEntropyFn.apply(logits, target.contiguous().long(), int(ignore_index),
                                  float(label_smoothing), reduction == "mean", acc)
+
+
+def pair_target(ya: torch.Tensor, yb: torch.Tensor, lam: torch.Tensor,
+                num_classes: int) -> torch.Tensor:
+    """The dense ``[B, C]`` target the pair form stands for:
+    ``lam * onehot(ya) + (1 - lam) * onehot(yb)`` (plain torch; the CPU path and the tests)."""
+    lam = lam.reshape(-1, 1)
+    return (lam * F.one_hot(ya, num_classes).to(lam.dtype) +
+            (1 - lam) * F.one_hot(yb, num_classes).to(lam.dtype))
+
+
+def cross_entropy_pair(logits: torch.Tensor, ya: torch.Tensor, yb: torch.Tensor,
+                       lam: torch.Tensor, label_smoothing: float = 0.0,
+                       reduction: str = "mean", acc: torch.Tensor | None = None) -> torch.Tensor:
+    """Cross-entropy against ``lam[r] * onehot(ya[r]) + (1 - lam[r]) * onehot(yb[r])`` -- the
+    target MixUp and CutMix produce (``tdp.data.BatchMix``) -- without ever building the
+    ``[B, C]`` target. ``ya``, ``yb`` are int64 ``[B]``, ``lam`` float32 ``[B]``. ``acc[1]`` counts
+    rows whose argmax is the heavier label (``ya`` when ``lam >= 0.5``)."""
+    if logits.dim() != 2:
+        raise ValueError("cross_entropy_pair expects [batch, classes] logits")
+    B = logits.shape[0]
+    if ya.dtype != torch.int64 or yb.dtype != torch.int64:
+        raise TypeError("cross_entropy_pair: ya and yb must be int64 class indices")
+    if not lam.is_floating_point():
+        raise TypeError("cross_entropy_pair: lam must be floating-point")
+    if tuple(ya.shape) != (B,) or tuple(yb.shape) != (B,) or tuple(lam.shape) != (B,):
+        raise ValueError(f"cross_entropy_pair: ya, yb and lam must be [{B}]")
+    if not logits.is_cuda:
+        dense = pair_target(ya, yb, lam.to(logits.dtype), logits.shape[1])
+        loss = F.cross_entropy(logits, dense, label_smoothing=label_smoothing,
+                               reduction=reduction)
+        if acc is not None:
+            with torch.no_grad():
+                acc[0] += F.cross_entropy(logits.detach(), dense, reduction="sum",
+                                          label_smoothing=label_smoothing)
+                acc[1] += (logits.argmax(1) == torch.where(lam >= 0.5, ya, yb)).sum()
+                acc[2] += B
+        return loss
+    logits = _soft_checks(logits, reduction)
+    if lam.dtype != torch.float32:
+        raise TypeError(f"native cross_entropy_pair: float32 lam only (got {lam.dtype})")
+    return _SoftCrossEntropyFn.apply(logits, None, ya.contiguous(), yb.contiguous(),
+                                     lam.detach().contiguous(), float(label_smoothing),
+                                     reduction == "mean", acc)
 
 
 _TICKETS: dict = {}
