@@ -101,6 +101,12 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
                 # both: its K loops split on the VALU beside MFMAs, and no packed-fp32 math
                 extra = ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang",
                          "-packed-fp32-ops"]
+            if s.name == "image_augment.hip":
+                # bit-exact against eager torch: f*a + g*b stays two multiplies and an add (the
+                # later flag wins; under =fast a contract pragma in the file is disregarded), and
+                # AutoContrast's 255.0f / span stays one correctly rounded division (hipcc's
+                # default, pinned here)
+                extra = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
             jobs_list.append([hipcc, f"--offload-arch={ARCH}", *common, "-ffp-contract=fast",
                               *extra, "-c", str(s), "-o", str(o)])
     for s in cpp_srcs:

@@ -2406,6 +2406,55 @@ Tensor image_crop_resize_op(const Tensor& x, const Tensor& box, const c10::optio
   return out;
 }
 
+// uint8 NHWC batch + device params int32 [N, 8] = (op, a0..a5, 0) -> the augmented batch
+// (csrc/image_augment.hip). Two launches and no read-back: the statistics launch returns the
+// partial-histogram workspace that the apply launch merges.
+void check_augment(const Tensor& x, const Tensor& params, const char* who) {
+  CHECK_GPU(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.scalar_type() == at::kByte && x.dim() == 4, who, ": x must be uint8 [N, H, W, C]");
+  TORCH_CHECK(x.size(3) == 1 || x.size(3) == 3, who, ": 1 or 3 channels");
+  TORCH_CHECK(x.size(0) <= 65535, who, ": at most 65535 samples per call");
+  TORCH_CHECK(x.size(1) >= 1 && x.size(2) >= 1 &&
+                  x.size(1) * x.size(2) * x.size(3) < (1LL << 31) - 4096,
+              who, ": a sample must be non-empty and stay below 2^31 bytes");
+  CHECK_GPU(params); CHECK_CONTIG(params);
+  TORCH_CHECK(params.device() == x.device(), who, ": params and x on different devices");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 &&
+                  params.size(0) == x.size(0) && params.size(1) == 8,
+              who, ": params must be int32 [N, 8] (op, a0..a5, 0)");
+}
+
+Tensor image_augment_stats_op(const Tensor& x, const Tensor& params) {
+  check_augment(x, params, "image_augment_stats");
+  const int N = (int)x.size(0), H = (int)x.size(1), W = (int)x.size(2), C = (int)x.size(3);
+  Tensor ws = at::empty({N, image_augment_chunks(H, W), 4, 256}, x.options().dtype(at::kInt));
+  if (N > 0) {
+    image_augment_stats(x.data_ptr<uint8_t>(), params.data_ptr<int>(),
+                        reinterpret_cast<uint32_t*>(ws.data_ptr<int>()), N, H, W, C, cur_stream());
+  }
+  return ws;
+}
+
+Tensor image_augment_apply_op(const Tensor& x, const Tensor& params,
+                              const c10::optional<Tensor>& ws) {
+  check_augment(x, params, "image_augment_apply");
+  const int N = (int)x.size(0), H = (int)x.size(1), W = (int)x.size(2), C = (int)x.size(3);
+  const uint32_t* wp = nullptr;
+  if (ws.has_value() && ws->defined()) {
+    CHECK_GPU(*ws); CHECK_CONTIG(*ws);
+    TORCH_CHECK(ws->device() == x.device() && ws->scalar_type() == at::kInt &&
+                    ws->numel() == (int64_t)N * image_augment_chunks(H, W) * 1024,
+                "image_augment_apply: ws must be image_augment_stats' result for this batch");
+    wp = reinterpret_cast<const uint32_t*>(ws->data_ptr<int>());
+  }
+  Tensor out = at::empty(x.sizes(), x.options());
+  if (N > 0) {
+    image_augment_apply(x.data_ptr<uint8_t>(), params.data_ptr<int>(), wp,
+                        out.data_ptr<uint8_t>(), N, H, W, C, cur_stream());
+  }
+  return out;
+}
+
 // the native prefetcher plus the tensors whose memory it reads
 struct PyHostLoader {
   Tensor data, labels;
@@ -2896,6 +2945,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("soft_ce_cap") = kSoftCeCap;
   m.def("mix_batch", &mix_batch_op, py::arg("x"), py::arg("perm"), py::arg("lam"),
         py::arg("boxes"));
+  m.def("image_augment_stats", &image_augment_stats_op, py::arg("x"), py::arg("params"));
+  m.def("image_augment_apply", &image_augment_apply_op, py::arg("x"), py::arg("params"),
+        py::arg("ws") = py::none());
 
   m.def("attn_fwd", &attn_fwd_op, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"));
   m.def("attn_bwd", &attn_bwd_op, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),

@@ -564,4 +564,22 @@ void soft_ce_scale(const float* dpre, const float* gout, long n, float* d, hipSt
 void mix_batch(const float* x, const void* perm, bool perm64, const float* lam, const int* box,
                float* out, int N, int C, int H, int W, bool nhwc, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------
+// Per-sample augmentation of a uint8 NHWC batch (csrc/image_augment.hip), out of place, C in
+// {1, 3}, H*W*C < 2^31 - 4096, N <= 65535. params [N][8] int32 = (op, a0..a5, 0):
+//   0 Identity | 1 Affine (a0..a5 = Q16 matrix in centred coordinates, nearest, fill 0)
+//   2 Brightness | 3 Color | 4 Contrast | 5 Sharpness (a0 = fp32 bits of the blend factor)
+//   6 Posterize (a0 = bits, clamped to 0..8) | 7 Solarize (a0 = fp32 bits of the threshold)
+//   8 AutoContrast | 9 Equalize; any other op is Identity.
+// image_augment_stats writes the partial histograms of the samples whose op needs them (4, 8, 9)
+// to ws, uint32 [N][image_augment_chunks(H, W)][4][256]; image_augment_apply reads them (ws may be
+// null when no sample needs statistics: such an op is then Identity). data/augment.py states the
+// arithmetic rule of every op; the result equals its reference_augment bit for bit.
+// ------------------------------------------------------------------------------------------------
+int image_augment_chunks(int H, int W);
+void image_augment_stats(const uint8_t* x, const int* params, uint32_t* ws, int N, int H, int W,
+                         int C, hipStream_t s);
+void image_augment_apply(const uint8_t* x, const int* params, const uint32_t* ws, uint8_t* out,
+                         int N, int H, int W, int C, hipStream_t s);
+
 }  // namespace tdp
