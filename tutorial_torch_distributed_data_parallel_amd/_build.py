@@ -107,6 +107,11 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
                 # AutoContrast's 255.0f / span stays one correctly rounded division (hipcc's
                 # default, pinned here)
                 extra = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
+            if s.name == "image_finish.hip":
+                # the Box-Muller rule of its "random" fill rounds every fp32 operation on its
+                # own, and its sqrtf is the correctly rounded one; the normalisation it shares
+                # with image_crop.hip (image_norm.h) spells its fused multiply-add out
+                extra = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
             jobs_list.append([hipcc, f"--offload-arch={ARCH}", *common, "-ffp-contract=fast",
                               *extra, "-c", str(s), "-o", str(o)])
     for s in cpp_srcs:

@@ -2361,12 +2361,14 @@ Tensor image_transform_op(const Tensor& x, const c10::optional<Tensor>& flip, in
 Tensor image_crop_resize_op(const Tensor& x, const Tensor& box, const c10::optional<Tensor>& flip,
                             int64_t Ho, int64_t Wo, std::vector<double> mean,
                             std::vector<double> stdv, bool round_u8, bool channels_last,
-                            double fill, bool check_boxes) {
+                            double fill, bool check_boxes, bool out_u8) {
   CHECK_GPU(x); CHECK_CONTIG(x);
   TORCH_CHECK(x.scalar_type() == at::kByte && x.dim() == 4, "image_crop_resize: uint8 [B,H,W,C]");
   const int B = (int)x.size(0), Hs = (int)x.size(1), Ws = (int)x.size(2), C = (int)x.size(3);
   TORCH_CHECK(C == 1 || C == 3 || C == 4, "image_crop_resize: 1, 3 or 4 channels");
-  TORCH_CHECK((int)mean.size() == C && (int)stdv.size() == C, "image_crop_resize: mean/std size");
+  TORCH_CHECK(out_u8 || ((int)mean.size() == C && (int)stdv.size() == C),
+              "image_crop_resize: mean/std size");
+  TORCH_CHECK(!out_u8 || round_u8, "image_crop_resize: a uint8 output is rounded");
   TORCH_CHECK(x.size(0) <= 65535, "image_crop_resize: at most 65535 samples per call");
   TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= kCropMaxExtent && Wo <= kCropMaxExtent,
               "image_crop_resize: output size out of range");
@@ -2391,6 +2393,12 @@ Tensor image_crop_resize_op(const Tensor& x, const Tensor& box, const c10::optio
     TORCH_CHECK(flip->scalar_type() == at::kByte && flip->numel() == B, "flip: uint8 [B]");
     fl = flip->data_ptr<uint8_t>();
   }
+  if (out_u8) {  // stop after the rounding and the flip: uint8 [B, Ho, Wo, C]
+    Tensor out = at::empty({B, Ho, Wo, C}, x.options());
+    image_crop_resize_u8(x.data_ptr<uint8_t>(), box.data_ptr<int>(), fl, out.data_ptr<uint8_t>(),
+                         B, Hs, Ws, C, (int)Ho, (int)Wo, (float)fill, cur_stream());
+    return out;
+  }
   ImageNorm nrm{};
   for (int c = 0; c < C; ++c) {
     nrm.mean[c] = (float)mean[c];
@@ -2403,6 +2411,55 @@ Tensor image_crop_resize_op(const Tensor& x, const Tensor& box, const c10::optio
   image_crop_resize(x.data_ptr<uint8_t>(), box.data_ptr<int>(), fl, out.data_ptr<float>(), B, Hs,
                     Ws, C, (int)Ho, (int)Wo, (float)fill, nrm, round_u8, channels_last,
                     cur_stream());
+  return out;
+}
+
+// uint8 NHWC batch (device; any byte alignment) -> normalised float [N, C, H, W] with sample n's
+// box (device int32 [N, 4]: top, left, h, w; h or w == 0: none; clamped by the kernel) erased
+// (csrc/image_finish.hip). mode 0: value[c] inside the box; 1: Philox normals from (seed, n + n_offset).
+Tensor image_normalize_erase_op(const Tensor& x, const c10::optional<Tensor>& box,
+                                std::vector<double> mean, std::vector<double> stdv,
+                                std::vector<double> value, int64_t mode, uint64_t seed,
+                                int64_t n_offset, bool channels_last) {
+  CHECK_GPU(x);
+  TORCH_CHECK(x.scalar_type() == at::kByte && x.dim() == 4 && x.is_contiguous(),
+              "image_normalize_erase: x must be contiguous uint8 [N, H, W, C]");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(C == 1 || C == 3 || C == 4, "image_normalize_erase: 1, 3 or 4 channels");
+  TORCH_CHECK(N <= 65535, "image_normalize_erase: at most 65535 samples per call");
+  TORCH_CHECK(H >= 1 && W >= 1 && H * W * C < (1LL << 31) - 4096,
+              "image_normalize_erase: a sample must be non-empty and stay below 2^31 bytes");
+  TORCH_CHECK((int64_t)mean.size() == C && (int64_t)stdv.size() == C &&
+                  (int64_t)value.size() == C, "image_normalize_erase: mean/std/value size");
+  TORCH_CHECK(mode == kEraseConst || mode == kEraseRandom, "image_normalize_erase: mode");
+  TORCH_CHECK(n_offset >= 0 && n_offset + N <= 0xFFFFFFFFLL, "image_normalize_erase: n_offset");
+  const int* bp = nullptr;
+  if (box.has_value() && box->defined()) {
+    CHECK_GPU(*box); CHECK_CONTIG(*box);
+    TORCH_CHECK(box->device() == x.device() && box->scalar_type() == at::kInt &&
+                    box->dim() == 2 && box->size(0) == N && box->size(1) == 4,
+                "image_normalize_erase: box must be int32 [N, 4] (top, left, h, w) on x's device");
+    bp = box->data_ptr<int>();
+  }
+  ImageNorm nrm{};
+  EraseFill fill{};
+  for (int c = 0; c < C; ++c) {
+    nrm.mean[c] = (float)mean[c];
+    nrm.inv_std[c] = (float)(1.0 / stdv[c]);
+    fill.value[c] = (float)value[c];
+  }
+  fill.seed_lo = (uint32_t)seed;
+  fill.seed_hi = (uint32_t)(seed >> 32);
+  fill.n_offset = (uint32_t)n_offset;
+  fill.mode = (int)mode;
+  auto opts = x.options().dtype(at::kFloat);
+  Tensor out = channels_last
+                   ? at::empty({N, C, H, W}, opts.memory_format(at::MemoryFormat::ChannelsLast))
+                   : at::empty({N, C, H, W}, opts);
+  if (N > 0) {
+    image_normalize_erase(x.data_ptr<uint8_t>(), bp, out.data_ptr<float>(), (int)N, (int)H,
+                          (int)W, (int)C, nrm, fill, channels_last, cur_stream());
+  }
   return out;
 }
 
@@ -2875,7 +2932,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("channels_last") = true);
   m.def("image_crop_resize", &image_crop_resize_op, py::arg("x"), py::arg("box"), py::arg("flip"),
         py::arg("Ho"), py::arg("Wo"), py::arg("mean"), py::arg("std"), py::arg("round_u8") = true,
-        py::arg("channels_last") = true, py::arg("fill") = 0.0, py::arg("check_boxes") = true);
+        py::arg("channels_last") = true, py::arg("fill") = 0.0, py::arg("check_boxes") = true,
+        py::arg("out_u8") = false);
+  m.def("image_normalize_erase", &image_normalize_erase_op, py::arg("x"), py::arg("box"),
+        py::arg("mean"), py::arg("std"), py::arg("value"), py::arg("mode") = 0,
+        py::arg("seed") = 0, py::arg("n_offset") = 0, py::arg("channels_last") = true);
   m.attr("CROP_TILE") = kCropTile;
   m.attr("CROP_STAGE_ROWS") = kCropStageRows;
   py::class_<PyHostLoader, std::shared_ptr<PyHostLoader>>(m, "HostBatchLoader")

@@ -38,11 +38,17 @@
 //   store    divide by the vertical weight sum, round, normalise, flip by mirroring the store
 //            column; every output element is written exactly once. channels_last: one thread
 //            stores its pixel's C floats (one 16-byte store at C = 4); NCHW: 64-byte row pieces.
+//   uint8    a third instantiation stops after the rounding and the flip and stores bytes into
+//            [B][Ho][Wo][C], the layout image_augment.hip and image_finish.hip read: the tile's
+//            bytes are laid out (mirrored when flipped) in the stage, which is free by then, and
+//            each tile row leaves as aligned 32-bit words. image_finish.hip applies the same
+//            image_normalize() to those bytes, so the two launches give the float form's bits.
 // Summation order is fixed (ascending taps, ascending chunks) and there are no atomics, so two
 // runs are bitwise equal. Every source read is bounds-checked against the image; the binding
 // rejects boxes with h, w < 1 or beyond kCropMaxExtent, and the kernel clamps them only so that a
 // box it was never meant to see cannot make the setup loop long.
 #include "common.h"
+#include "image_norm.h"
 #include "kernels.h"
 
 namespace tdp {
@@ -98,7 +104,7 @@ __device__ __forceinline__ void load_pixel(const uint8_t* p, float (&v)[C]) {
   }
 }
 
-template <int C, bool CL>
+template <int C, bool CL, bool U8>
 __global__ __launch_bounds__(256) void image_crop_resize_kernel(
     const uint8_t* __restrict__ x, const int* __restrict__ box, const uint8_t* __restrict__ flip,
     float* __restrict__ out, int Hs, int Ws, int Ho, int Wo, float fill, ImageNorm nrm,
@@ -174,6 +180,36 @@ __global__ __launch_bounds__(256) void image_crop_resize_kernel(
     __syncthreads();  // the next chunk overwrites the stage
   }
 
+  if constexpr (U8) {
+    // uint8 form: stop after the flip. The stage is free after the loop's last barrier; the tile's
+    // bytes go there, mirrored inside the tile when flipped, and each tile row leaves as aligned
+    // 32-bit words, with single bytes at a ragged end.
+    uint8_t* tile8 = reinterpret_cast<uint8_t*>(stage);
+    uint8_t* o8 = reinterpret_cast<uint8_t*>(out);  // [B][Ho][Wo][C]
+    const bool fl = flip != nullptr && flip[b];
+    const int ncols = min(kT, Wo - tx0), len = ncols * C;
+    if (pix_ok) {
+      uint8_t* t = tile8 + (sub * kT + (fl ? ncols - 1 - oxl : oxl)) * C;
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        t[c] = (uint8_t)(int)fminf(fmaxf(rintf(acc[c] / vsum), 0.f), 255.f);
+    }
+    __syncthreads();
+    if (oy >= Ho) return;
+    const uint8_t* trow = tile8 + sub * kT * C;
+    uint8_t* orow = o8 + (((long)b * Ho + oy) * Wo + (fl ? Wo - tx0 - ncols : tx0)) * C;
+    const int mis = (int)((uintptr_t)orow & 3);
+    for (int e0 = 4 * oxl - mis; e0 < len; e0 += 4 * kT) {
+      if (e0 >= 0 && e0 + 4 <= len) {
+        *reinterpret_cast<uint32_t*>(orow + e0) =
+            (uint32_t)trow[e0] | ((uint32_t)trow[e0 + 1] << 8) | ((uint32_t)trow[e0 + 2] << 16) |
+            ((uint32_t)trow[e0 + 3] << 24);
+      } else {
+        for (int e = max(e0, 0); e < min(e0 + 4, len); ++e) orow[e] = trow[e];
+      }
+    }
+    return;
+  }
   if (!pix_ok) return;
   const int wo = (flip != nullptr && flip[b]) ? Wo - 1 - ox : ox;
   float v[C];
@@ -181,7 +217,7 @@ __global__ __launch_bounds__(256) void image_crop_resize_kernel(
   for (int c = 0; c < C; ++c) {
     v[c] = acc[c] / vsum;
     if (round_u8) v[c] = rintf(v[c]);
-    v[c] = (v[c] * (1.f / 255.f) - nrm.mean[c]) * nrm.inv_std[c];
+    v[c] = image_normalize(v[c], nrm.mean[c], nrm.inv_std[c]);
   }
   if (CL) {  // [B][Ho][Wo][C]
     float* dst = out + (((long)b * Ho + oy) * Wo + wo) * C;
@@ -197,12 +233,12 @@ __global__ __launch_bounds__(256) void image_crop_resize_kernel(
   }
 }
 
-template <int C, bool CL>
+template <int C, bool CL, bool U8 = false>
 void launch_crop(const uint8_t* x, const int* box, const uint8_t* flip, float* out, int B, int Hs,
                  int Ws, int Ho, int Wo, float fill, const ImageNorm& nrm, int round_u8,
                  hipStream_t s) {
   const dim3 grid((unsigned)ceil_div(Wo, kT), (unsigned)ceil_div(Ho, kT), (unsigned)B);
-  hipLaunchKernelGGL((image_crop_resize_kernel<C, CL>), grid, dim3(256), 0, s, x, box, flip, out,
+  hipLaunchKernelGGL((image_crop_resize_kernel<C, CL, U8>), grid, dim3(256), 0, s, x, box, flip, out,
                      Hs, Ws, Ho, Wo, fill, nrm, round_u8);
 }
 
@@ -223,6 +259,20 @@ void image_crop_resize(const uint8_t* x, const int* box, const uint8_t* flip, fl
     if (channels_last) TDP_CROP(4, true); else TDP_CROP(4, false);
   }
 #undef TDP_CROP
+}
+
+void image_crop_resize_u8(const uint8_t* x, const int* box, const uint8_t* flip, uint8_t* out,
+                          int B, int Hs, int Ws, int C, int Ho, int Wo, float fill,
+                          hipStream_t s) {
+  if ((long)B * Ho * Wo <= 0) return;
+  float* o = reinterpret_cast<float*>(out);  // the uint8 form reads it back as bytes
+  const ImageNorm nrm{};
+#define TDP_CROP8(CC) \
+  launch_crop<CC, true, true>(x, box, flip, o, B, Hs, Ws, Ho, Wo, fill, nrm, 1, s)
+  if (C == 3) TDP_CROP8(3);
+  else if (C == 1) TDP_CROP8(1);
+  else if (C == 4) TDP_CROP8(4);
+#undef TDP_CROP8
 }
 
 }  // namespace tdp

@@ -386,6 +386,25 @@ constexpr int kCropMaxExtent = 1 << 23;  // largest box / output extent (integer
 void image_crop_resize(const uint8_t* x, const int* box, const uint8_t* flip, float* out, int B,
                        int Hs, int Ws, int C, int Ho, int Wo, float fill, const ImageNorm& nrm,
                        bool round_u8, bool channels_last, hipStream_t s);
+// The same kernel stopped after the rounding and the flip: uint8 [B][Ho][Wo][C], the layout
+// image_augment_* and image_normalize_erase read.
+void image_crop_resize_u8(const uint8_t* x, const int* box, const uint8_t* flip, uint8_t* out,
+                          int B, int Hs, int Ws, int C, int Ho, int Wo, float fill, hipStream_t s);
+// ToTensor + Normalize + RandomErasing in one launch (csrc/image_finish.hip): uint8 [N][H][W][C]
+// -> float [N][C][H][W] (or channels_last), image_normalize() outside sample n's box
+// box[4n..4n+3] = (top, left, h, w), clamped to the image, h == 0 or w == 0 or box == nullptr:
+// no erase. Inside: value[c] as given (mode kEraseConst) or a standard normal from Philox4x32-10
+// keyed by the seed with counter (e >> 2, 0, n + n_offset, 0 | 1), e = (c H + i) W + j
+// (kEraseRandom). C in {1, 3, 4}, N <= 65535, H W C < 2^31.
+enum EraseMode : int { kEraseConst = 0, kEraseRandom = 1 };
+struct EraseFill {
+  float value[4];
+  uint32_t seed_lo, seed_hi, n_offset;
+  int mode;
+};
+void image_normalize_erase(const uint8_t* x, const int* box, float* out, int N, int H, int W,
+                           int C, const ImageNorm& nrm, const EraseFill& fill, bool channels_last,
+                           hipStream_t s);
 void bf16_to_f32_copy(const uint16_t* x, float* y, long n, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------

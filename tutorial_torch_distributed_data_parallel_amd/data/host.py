@@ -177,11 +177,12 @@ def _check_boxes(boxes: torch.Tensor, n: int) -> None:
 
 
 def reference_crop_resize(x_u8: torch.Tensor, boxes: torch.Tensor, flip: torch.Tensor | None,
-                          size, mean, std, round_u8: bool = True,
-                          fill: float = 0.0) -> torch.Tensor:
+                          size, mean, std, round_u8: bool = True, fill: float = 0.0,
+                          out_dtype=torch.float32) -> torch.Tensor:
     """torch implementation of image_crop_resize (the CPU path): pad with ``fill`` as far as
     the boxes reach, slice each sample's box, antialiased bilinear resize, round, flip,
-    normalise; [B,H,W,C] uint8 -> [B,C,Ho,Wo] float32."""
+    normalise; [B,H,W,C] uint8 -> [B,C,Ho,Wo] float32, or with ``out_dtype=torch.uint8`` the
+    rounded, flipped grey levels as uint8 [B,Ho,Wo,C]."""
     B, H, W, _ = x_u8.shape
     bx = boxes.tolist()
     pt = max([0] + [-t for t, _, _, _ in bx])
@@ -197,6 +198,8 @@ def reference_crop_resize(x_u8: torch.Tensor, boxes: torch.Tensor, flip: torch.T
         y = y.round()
     if flip is not None:
         y = torch.where(flip.bool().view(-1, 1, 1, 1), y.flip(-1), y)
+    if out_dtype == torch.uint8:
+        return y.round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
     m = torch.tensor(mean, dtype=torch.float32, device=y.device).view(1, -1, 1, 1)
     s = torch.tensor(std, dtype=torch.float32, device=y.device).view(1, -1, 1, 1)
     return (y / 255.0 - m) / s
@@ -204,13 +207,31 @@ def reference_crop_resize(x_u8: torch.Tensor, boxes: torch.Tensor, flip: torch.T
 
 def crop_resize(x_u8: torch.Tensor, boxes: torch.Tensor, flip: torch.Tensor | None, size,
                 mean, std, round_u8: bool = True, channels_last: bool = True,
-                fill: float = 0.0) -> torch.Tensor:
+                fill: float = 0.0, out_dtype=torch.float32) -> torch.Tensor:
     """Crop sample b of ``x_u8`` [B,H,W,C] to ``boxes[b] = (top, left, h, w)`` (int32; parts
     outside the image read ``fill``), resize the crop to ``size`` with the antialiased triangle
     filter, round like a uint8 image, flip where ``flip[b]``, normalise. On a GPU tensor this is
     the native kernel; host boxes are validated here and uploaded without a sync, device boxes
-    are read back once by the binding to validate them."""
+    are read back once by the binding to validate them.
+
+    ``out_dtype=torch.uint8`` stops after the rounding and the flip and returns the grey levels
+    as uint8 [B,Ho,Wo,C], the layout ``augment_batch`` and ``normalize_erase`` read (``mean``,
+    ``std`` and ``channels_last`` are ignored; ``round_u8=False`` is an error);
+    ``normalize_erase`` of that result is the float32 result bit for bit."""
+    return _crop_resize(x_u8, boxes, flip, size, mean, std, round_u8, channels_last, fill,
+                        out_dtype, check_device_boxes=True)
+
+
+def _crop_resize(x_u8, boxes, flip, size, mean, std, round_u8, channels_last, fill, out_dtype,
+                 check_device_boxes):
+    """crop_resize; ``check_device_boxes=False`` trusts device boxes (no read-back, so the call
+    can be captured): the kernel clamps h, w to at least 1."""
     size = _norm_size(size)
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"crop_resize: out_dtype must be float32 or uint8 (got {out_dtype})")
+    u8 = out_dtype == torch.uint8
+    if u8 and not round_u8:
+        raise ValueError("crop_resize: a uint8 output is rounded; round_u8=False contradicts it")
     if x_u8.is_cuda:
         host_boxes = not boxes.is_cuda
         if host_boxes:
@@ -218,10 +239,11 @@ def crop_resize(x_u8: torch.Tensor, boxes: torch.Tensor, flip: torch.Tensor | No
             boxes = boxes.to(x_u8.device, non_blocking=True)
         return native().image_crop_resize(x_u8, boxes, flip, size[0], size[1], list(mean),
                                           list(std), round_u8, channels_last, float(fill),
-                                          check_boxes=not host_boxes)
+                                          check_boxes=not host_boxes and check_device_boxes,
+                                          out_u8=u8)
     _check_boxes(boxes, x_u8.shape[0])
-    y = reference_crop_resize(x_u8, boxes, flip, size, mean, std, round_u8, fill)
-    return y.contiguous(memory_format=torch.channels_last) if channels_last else y
+    y = reference_crop_resize(x_u8, boxes, flip, size, mean, std, round_u8, fill, out_dtype)
+    return y if u8 else y.contiguous(memory_format=torch.channels_last) if channels_last else y
 
 
 def resized_crop_boxes(n: int, H: int, W: int, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3),
@@ -281,14 +303,25 @@ class CropTransform:
 
     The boxes of each batch come from the transform's own CPU generator, which ``start_epoch``
     reseeds (PrefetchLoader does so with its per-(seed, epoch) value), and reach the GPU through
-    a pinned buffer and a non-blocking copy: no host sync."""
+    a pinned buffer and a non-blocking copy: no host sync.
+
+    ``augment`` (e.g. a ``TrivialAugment``: anything with ``draw(n, H, W)`` giving
+    ``augment_batch`` params) and ``erase`` (a ``RandomErasing``) switch to torchvision's order:
+    the crop kernel writes the uint8 crop, the augmentation runs on that crop (its TranslateX/Y
+    pixels and its statistics are the crop's), and ``normalize_erase`` normalises and erases.
+    With both ``None`` the transform is the single fused launch. ``apply`` runs the same steps on
+    parameters the caller supplies (host or device tensors)."""
 
     def __init__(self, size=224, crop: str = "random_resized", scale=(0.08, 1.0),
                  ratio=(3 / 4, 4 / 3), padding: int = 4, fraction: float = 0.875,
                  flip_p: float = 0.5, mean=CIFAR_MEAN, std=CIFAR_STD, round_u8: bool = True,
-                 channels_last: bool = True):
+                 channels_last: bool = True, augment=None, erase=None):
         if crop not in ("random_resized", "random_pad", "center"):
             raise ValueError(f"unknown crop {crop!r}")
+        if (augment is not None or erase is not None) and not round_u8:
+            raise ValueError("CropTransform: augment / erase work on the uint8 crop; "
+                             "round_u8=False contradicts it")
+        self.augment, self.erase = augment, erase
         self.size, self.crop = _norm_size(size), crop
         self.scale, self.ratio = tuple(scale), tuple(ratio)
         self.padding, self.fraction = int(padding), float(fraction)
@@ -298,6 +331,9 @@ class CropTransform:
 
     def start_epoch(self, seed: int) -> None:
         self._gen.manual_seed(int(seed))
+        for k, t in enumerate((self.augment, self.erase), 1):
+            if hasattr(t, "start_epoch"):
+                t.start_epoch(int(seed) + k)
 
     def boxes(self, n: int, H: int, W: int) -> torch.Tensor:
         if self.crop == "random_resized":
@@ -312,8 +348,31 @@ class CropTransform:
         if x_u8.is_cuda:
             # torch's pinned-host cache keeps the buffer alive until the copy has run
             boxes = torch.empty_like(boxes, pin_memory=True).copy_(boxes)
-        return crop_resize(x_u8, boxes, flip if self.flip_p > 0 else None, self.size, self.mean,
-                           self.std, self.round_u8, self.channels_last)
+        flip = flip if self.flip_p > 0 else None
+        if self.augment is None and self.erase is None:
+            return crop_resize(x_u8, boxes, flip, self.size, self.mean, self.std, self.round_u8,
+                               self.channels_last)
+        params = None if self.augment is None else self.augment.draw(n, *self.size)
+        eboxes, seed = (None, 0) if self.erase is None else self.erase.draw(n, *self.size)
+        return self.apply(x_u8, flip, boxes, params, eboxes, seed)
+
+    def apply(self, x_u8: torch.Tensor, flip: torch.Tensor | None, boxes: torch.Tensor,
+              params: torch.Tensor | None = None, erase_boxes: torch.Tensor | None = None,
+              seed: int = 0) -> torch.Tensor:
+        """Crop to uint8 with ``boxes``, ``augment_batch`` with ``params`` (if given),
+        ``normalize_erase`` with ``erase_boxes`` and ``seed``. Host tensors are validated and
+        uploaded; device tensors are trusted and nothing is read back, so the call can be
+        captured in a graph (where ``seed`` is fixed at capture)."""
+        from .augment import augment_batch
+        from .erase import normalize_erase
+
+        u8 = _crop_resize(x_u8, boxes, flip, self.size, self.mean, self.std, True,
+                          self.channels_last, 0.0, torch.uint8, check_device_boxes=False)
+        if params is not None:
+            u8 = augment_batch(u8, params)
+        return normalize_erase(u8, self.mean, self.std, erase_boxes,
+                               0.0 if self.erase is None else self.erase.value, seed,
+                               self.channels_last)
 
 
 def _epoch_seed(seed: int, epoch: int) -> int:
